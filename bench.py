@@ -2,7 +2,12 @@
 """bench.py -- BASELINE config 2: 3840x2160 f16 RGBA, Rec.709 transfer LUT + RGB->Y'PbPr matrix on
 each of 2 layers, 2-layer alpha-over, f16 out; frames resident in HBM; Mpixels/s.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else the script
+measures or checks: the per-rank fixture proof, the same-run copy yardstick, configs 3 / 4 / 5 as `extra` records and the
+CPU baseline.  --dump-outputs DIR writes, after the timed steps, a fixed sample of the output frames of the last step
+(see dump_outputs), so that two builds can be compared output for output.
 
 One process per GPU.  Under `torch.distributed.run` the ranks are the launcher's (RANK / LOCAL_RANK / WORLD_SIZE);
 started plainly with --gpus N > 1, this script starts its N ranks itself (canvas_amd/launch.py) before anything touches
@@ -15,8 +20,8 @@ cvs_chain_color_over_f16_dev; the library cuts it into launches of about eight f
 The input ring (--ring frame sets, default 8 x 199 MB = 1.6 GB) is several times the 256 MiB Infinity Cache, so every
 launch streams from HBM (a 64-frame step walks the ring eight times).
 
-Every rank proves its pixels: the output of its first frame (global frame = rank) is downloaded whole and its SHA-256
-compared with the committed fixture tests/golden/stream_frames_sha256.json (made by the oracle in the build container);
+With --full every rank proves its pixels: the output of its first frame (global frame = rank) is downloaded whole and its
+SHA-256 compared with the committed fixture tests/golden/stream_frames_sha256.json (made by the oracle, tests/golden/make_checksums.py);
 the JSON line carries `ranks_verified`.  After the timed config-2 region the other BASELINE configs (3, 4, 5) run briefly
 on every rank, each over more than 1.5 GB of rotating frames, and appear as `extra` sub-records.
 """
@@ -54,7 +59,15 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-extra", action="store_true", help="skip the config 3 / 4 / 5 sub-records")
     ap.add_argument("--extra-seconds", type=float, default=1.5, help="timed region of each extra config, per rank (long enough for a 5 s SMI sampler to see the GPU busy)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the fixture proof, the copy yardstick, the config 3 / 4 / 5 extras and the CPU baseline "
+                         "(--no-extra / --no-cpu-baseline leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's output frames to DIR as .npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def build_cpu_baseline():
@@ -163,12 +176,42 @@ def spread(ms):
             "min": round(float(min(ms)), 4), "max": round(float(max(ms)), 4), "n": len(ms)}
 
 
+DUMP_BYTES = 56 << 20          # everything --dump-outputs writes stays under 64 MB
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(dirname, ring, my_frames, step_index, batch, stream):
+    """What the caller of the timed path receives from step `step_index`: the output frames that step rendered (the ring
+    slots its batch touched, in the order of first use), as f32 RGBA.  A 4K frame is 132 MB in f32, so every frame is
+    sampled at the same pixels, drawn once from a fixed seed (all pixels when they fit):
+      output_pixels.npy       float32 (frames, pixels, 4)   RGBA of the sampled pixels, converted exactly from f16
+      output_pixel_index.npy  float64 (pixels,)             row-major pixel index y * width + x
+      output_frame.npy        float64 (frames,)             global stream frame of each output"""
+    slots = []
+    for b in range(batch):
+        j = (step_index * batch + b) % len(ring)
+        if j not in slots:
+            slots.append(j)
+    out0 = ring[slots[0]][0]
+    npx = out0.width * out0.height
+    k = min(npx, DUMP_BYTES // (16 * len(slots) + 8))
+    pick = np.arange(npx) if k == npx else np.sort(np.random.Generator(np.random.Philox(DUMP_SEED)).choice(npx, k, replace=False))
+    px = np.empty((len(slots), k, 4), np.float32)
+    for a, j in enumerate(slots):
+        codes = ring[j][0].download(stream).array.reshape(npx, 4)
+        px[a] = codes[pick].view(np.float16).astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "output_pixels.npy"), px)
+    np.save(os.path.join(dirname, "output_pixel_index.npy"), pick.astype(np.float64))
+    np.save(os.path.join(dirname, "output_frame.npy"), np.array([my_frames[j] for j in slots], np.float64))
+
+
 def main():
     args = parse()
     from canvas_amd import launch
     launch.ensure_ranks(args.gpus)          # --gpus N without a launcher: become N ranks (never returns in the parent)
     native_oracle = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.full and not args.no_cpu_baseline:
         native_oracle = build_cpu_baseline()                           # (the checker, built before the first GPU call)
 
     # stdout carries exactly ONE line, the JSON result: libraries that write banners there (RCCL prints its version,
@@ -259,11 +302,16 @@ def main():
     elapsed = time.perf_counter() - t0
     step_ms = timed.ms()
 
-    # ---- every rank proves its pixels: whole first frame, SHA-256 against the committed fixture
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ring, my_frames, args.warmup + args.steps - 1, args.batch, stream)
+
+    # ---- (--full) every rank proves its pixels: whole first frame, SHA-256 against the committed fixture
     standard = (w, h, nl) == (3840, 2160, 2) and not args.translucent_base
-    digest = verify.canon_sha256(ring[0][0].download(stream).array)
-    want = verify.stream_fixture("config2_3840x2160", my_frames[0]) if standard else None
-    verified = -1 if want is None else int(digest == want)            # -1: no fixture for this shape / frame
+    digest, verified = "0" * 64, -2                                     # -2: not checked (plain run)
+    if args.full:
+        digest = verify.canon_sha256(ring[0][0].download(stream).array)
+        want = verify.stream_fixture("config2_3840x2160", my_frames[0]) if standard else None
+        verified = -1 if want is None else int(digest == want)        # -1: no fixture for this shape / frame
 
     px_per_step = args.batch * w * h
     algo_bytes = px_per_step * BYTES_PER_PIXEL_PER_LAYER * (nl + 1)
@@ -273,7 +321,7 @@ def main():
 
     # same-run yardstick for this box: plain device-to-device copies of the same frames
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             e0, e1 = lib.cvs_event_create(), lib.cvs_event_create()
             pairs = [(ring[i % len(ring)][0], ring[(i + 1) % len(ring)][1][0]) for i in range(32)]
@@ -289,7 +337,7 @@ def main():
             copy_gbs = None
 
     extra = []
-    if not args.no_extra and standard:
+    if args.full and not args.no_extra and standard:
         from bench_extra import run_extras
         extra = run_extras(lib, dist, rank, world, stream, ring, my_frames, m, args.extra_seconds)
 
@@ -339,16 +387,17 @@ def main():
                                  "achieved = %d B/px x %d px per step / HIP-event step time on the launch stream (rank 0), i.e. launch "
                                  "durations plus the gaps between them" % (args.batch, launches_per_step, BYTES_PER_PIXEL_PER_LAYER * (nl + 1), px_per_step)},
             "frames_per_rank": [s[0] for s in stats],
-            "ranks_verified": sum(1 for s in stats if int(s[3]) == 1),
-            "per_rank": [{"rank": r, "first_frame": r, "sha256_52bit": "%013x" % s[1],
-                          "verified": {1: True, 0: False}.get(int(s[3]), "no fixture"),
+            "ranks_verified": sum(1 for s in stats if int(s[3]) == 1) if args.full else None,
+            "per_rank": [{"rank": r, "first_frame": r, "sha256_52bit": "%013x" % s[1] if args.full else None,
+                          "verified": {1: True, 0: False, -2: "not checked (--full)"}.get(int(s[3]), "no fixture"),
                           "seconds": round(s[2], 4), "step_ms_mean": round(s[4], 4), "frac": round(s[5], 4)} for r, s in enumerate(stats)],
-            "verified_against_fixture": all(int(s[3]) == 1 for s in stats) if standard else "no fixture for this shape",
+            "verified_against_fixture": ("not checked (--full)" if not args.full else
+                                         all(int(s[3]) == 1 for s in stats) if standard else "no fixture for this shape"),
             "device": lib.cvs_device_name().decode(),
         }
         if extra:
             res["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds, native_oracle)
             except Exception as e:

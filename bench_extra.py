@@ -1,4 +1,4 @@
-"""The other BASELINE configs as sub-records of bench.py's JSON line (`extra`), measured after the timed config-2 region
+"""The other BASELINE configs as sub-records of bench.py --full's JSON line (`extra`), measured after the timed config-2 region
 on every rank of the run (frames shard the same way: global frame g -> rank g % N, nothing exchanged on the data path).
 
 Every workload rotates over more than 1.5 GB of resident frames, so nothing it reads is served from the 256 MiB Infinity

@@ -327,13 +327,34 @@ def test_extension_links_only_the_library_not_the_oracle():
 
 
 def test_reference_own_frame_function_tests_run_unmodified(process):
-    """Where the reference tree is mounted (this container, not the GPU box): its own unittest file for frame
-    functions, loaded as it is and run against THIS module -- LerpFunc and AnimationFunc need no pixels."""
+    """The reference's own unittest file for frame functions against THIS module -- LerpFunc and AnimationFunc need no
+    pixels.  Its known answers are checked everywhere from tests/golden/; where the reference tree is mounted the file
+    itself is loaded as it is and run."""
     import importlib.util
     import unittest
+    from tests.test_reference_python_tests import reference_kats
+    kats = reference_kats("frame_func")
+    near = lambda got, want: list(got) == pytest.approx(list(want), abs=5e-8)        # noqa: E731  (assertAlmostEqual: 7 places)
+    lerp = kats["lerp"]
+    func = process.LerpFunc(tuple(lerp["start"]), tuple(lerp["end"]), lerp["length"])
+    for frame, want in lerp["single"]:
+        assert near(func.get_values(frame)[0], want), (frame, want)
+    got = func.get_values(lerp["batch_frames"])
+    assert len(got) == len(lerp["batch_values"]) and all(near(g, w) for g, w in zip(got, lerp["batch_values"]))
+    anim = process.AnimationFunc()
+    for kind, frame, value in kats["animation"]["points"]:
+        anim.add(process.AnimationPoint(getattr(process, kind), frame, value))
+    for frame, want in kats["animation"]["queries"]:
+        assert anim.get_values(frame)[0][0] == pytest.approx(want, abs=5e-8), (frame, want)
+    move = kats["animation_move"]
+    anim = process.AnimationFunc()
+    points = [anim.add(getattr(process, kind), frame, value) for kind, frame, value in move["added"]]
+    assert [anim[i] for i in range(len(points))] == [points[i] for i in move["order"]]
+    points[move["move"]["point"]].frame = move["move"]["frame"]
+    assert [anim[i] for i in range(len(points))] == [points[i] for i in move["order_after"]]
     path = "/root/reference/tests/process/frame_func.py"
     if not os.path.exists(path):
-        pytest.skip("reference tree not present")
+        return
     spec = importlib.util.spec_from_file_location("reference_frame_func_tests", path)
     mod = importlib.util.module_from_spec(spec)
     import sys

@@ -183,10 +183,13 @@ def test_eight_ranks_one_result_line_and_tagged_stderr(tmp_path):
     assert all(l.startswith("[rank ") for l in p.stderr.splitlines() if l.strip())
 
 
-def test_rank_placement_from_a_sysfs_tree(tmp_path):
+def test_rank_placement_from_a_sysfs_tree(tmp_path, monkeypatch):
     """place_rank reads the KFD topology and the PCI device of the rank's GPU from sysfs (no HIP call): two GPUs on node 0,
-    two on node 1 of a made-up tree -> each rank gets the CPUs local to its GPU, shared with its node mate."""
+    two on node 1 of a made-up tree -> each rank gets the CPUs local to its GPU, shared with its node mate.  The tree is the
+    whole machine here: a device mask of the host running the test (one GPU handed to the job) does not apply to it."""
     from canvas_amd import launch
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
+        monkeypatch.delenv(var, raising=False)
     root = tmp_path / "sys"
     gpus = [(0x0300, 0, "0-3"), (0x0400, 0, "0-3"), (0x8300, 1, "4-7"), (0x8400, 1, "4-7")]
     nodes = root / "class" / "kfd" / "kfd" / "topology" / "nodes"

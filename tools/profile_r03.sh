@@ -15,7 +15,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $B > $O/trac
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B --steps 3 --warmup 1 > $O/fetch_bench.json 2> $O/fetch.log || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -- $B --steps 3 --warmup 1 > $O/write_bench.json 2> $O/write.log || exit 1
 echo "chain done"
-E="python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.1"
+E="python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/x_trace -- $E > $O/x_trace_bench.json 2> $O/x_trace.log || exit 1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/x_fetch -- $E > $O/x_fetch_bench.json 2> $O/x_fetch.log || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/x_write -- $E > $O/x_write_bench.json 2> $O/x_write.log || exit 1

@@ -17,10 +17,10 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_trace -- $B > $O/t_
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/t_fetch -- $B --steps 3 --warmup 1 > $O/t_fetch_bench.json 2> $O/t_fetch.log || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/t_write -- $B --steps 3 --warmup 1 > $O/t_write_bench.json 2> $O/t_write.log || exit 1
 echo "chain done"
-E="python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.5"
+E="python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.5"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/x_trace -- $E > $O/x_trace_bench.json 2> $O/x_trace.log || exit 1
 echo "extras trace done"
-E="python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.1"
+E="python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.1"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/x_fetch -- $E > $O/x_fetch_bench.json 2> $O/x_fetch.log || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/x_write -- $E > $O/x_write_bench.json 2> $O/x_write.log || exit 1
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVES --output-format csv -d $O/x_sq1 -- $E > $O/x_sq1_bench.json 2> $O/x_sq1.log || exit 1

@@ -198,7 +198,7 @@ for pat, lb, sb, algo_b, note in KERNELS:
     xs[pat] = rec
     print("%-34s %7.1f us  frac(alg) %.3f  traffic x%s" % (pat, rec["duration"]["mean_us"], rec["frac_of_8TBps_on_algorithmic_bytes"],
                                                            rec.get("traffic", {}).get("ratio_to_algorithmic")))
-json.dump({"command": "rocprofv3 --kernel-trace [--stats | --pmc <one group>] -- python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.1",
+json.dump({"command": "rocprofv3 --kernel-trace [--stats | --pmc <one group>] -- python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.1",
            "kernels": xs, "extras_of_the_traced_run": [{k: e.get(k) for k in ("config", "ms_per_frame_per_gpu", "roofline")} for e in xbench.get("extra", [])]},
           open(os.path.join(DST, "extras_kernels.json"), "w"), indent=1)
 shutil.copy(one("x_trace/**/*kernel_stats.csv"), os.path.join(DST, "extras_kernel_stats.csv"))

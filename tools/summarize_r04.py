@@ -213,7 +213,7 @@ for pat, recs, fpl, algo_b, note in PLAN:
         xs["%s [%s]" % (name, pat.split("<")[0])] = rec
         print("%-44s trace %7.2f us/frame  bench %7.2f  %s  valu busy %s" % (name + " " + pat.split("<")[0], per_frame_us, bench_us,
               "nests" if rec.get("trace_fits_inside_bench", True) else "DOES NOT NEST", rec.get("valu_busy_share_of_simd_time")))
-json.dump({"command": "rocprofv3 --kernel-trace [--stats | --pmc <one group>] -- python3 bench.py --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.5 (0.1 for the counter runs)",
+json.dump({"command": "rocprofv3 --kernel-trace [--stats | --pmc <one group>] -- python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 2 --extra-seconds 0.5 (0.1 for the counter runs)",
            "how": "per-frame time from the trace = span of the kernel's launches in the timed region (first quarter dropped) / frames processed, two streams overlapping as in the bench; "
                   "counters: mean per launch of the same region; bytes are labelled per launch or per frame",
            "kernels": xs, "extras_of_the_traced_run": [{k: e.get(k) for k in ("config", "arithmetic", "ms_per_frame_per_gpu", "roofline", "ranks_verified")} for e in xbench.get("extra", [])]},
