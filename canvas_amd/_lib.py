@@ -162,6 +162,8 @@ SIGNATURES = {
     "video_subsample_dv": (P(coded_image), [_F16]),
     "cvs_reconstruct_dv_dev": (C.c_int, [_F16, P(coded_image), _vp]),
     "cvs_subsample_dv_dev": (C.c_int, [P(coded_image), _F16, C.c_int, _vp]),
+    "video_subsample_mpeg2": (P(coded_image), [_F16]),
+    "cvs_subsample_mpeg2_dev": (C.c_int, [P(coded_image), _F16, C.c_int, C.c_int, _vp]),
     "cvs_frame_to_bytes_dev": (C.c_int, [_vp, _F16, C.c_int, C.c_int, _vp]),
     "video_frame_to_bytes": (C.c_int, [_vp, _F16, C.c_int, C.c_int]),
     "cvs_frame_to_rgba8_intent_dev": (C.c_int, [_vp, _F16, C.c_int, C.c_float, _vp]),

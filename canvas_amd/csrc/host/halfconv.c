@@ -184,10 +184,9 @@ unsigned cvs_lut_generation(int which) {
     return (which >= 0 && which < CVS_LUT_COUNT) ? __atomic_load_n(&lut_gen2[lut_row(which)][which], __ATOMIC_ACQUIRE) * 2u + (unsigned)lut_row(which) : 0;
 }
 
-static int ensure_lut(int which) {
+/* cvs_enter() done */
+static int ensure_lut_row(int which, int row) {
     if (which < 0 || which >= CVS_LUT_COUNT) { cvs_set_error("no such transfer table: %d", which); return -1; }
-    if (cvs_enter() != 0) return -1;
-    const int row = lut_row(which);
     pthread_mutex_lock(&lut_lock);
     int rc = 0;
     if (!lut_gen2[row][which]) {
@@ -209,6 +208,11 @@ static int ensure_lut(int which) {
     pthread_mutex_unlock(&lut_lock);
     return rc;
 }
+
+static int ensure_lut(int which) { return cvs_enter() != 0 ? -1 : ensure_lut_row(which, lut_row(which)); }   /* lut_row: the flavour cvs_enter() took */
+
+/* the separate-arithmetic table whatever the call's flavour: for kernels that are flavour-independent by contract */
+const half *cvs_lut_device_separate(int which) { return cvs_enter() == 0 && ensure_lut_row(which, 0) == 0 ? lut_dev3[cvs_ctx()][0][which] : NULL; }
 
 CVS_EXPORT const half *cvs_lut_device(int which) { return ensure_lut(which) == 0 ? lut_dev3[cvs_ctx()][lut_row(which)][which] : NULL; }
 CVS_EXPORT const half *cvs_lut_host(int which) { return ensure_lut(which) == 0 ? lut_host2[lut_row(which)][which] : NULL; }

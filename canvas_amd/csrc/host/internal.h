@@ -107,5 +107,8 @@ void cvs_stage_free(cvs_staged *st);
 
 /* device LUT for an id, NULL for CVS_LUT_NONE; builds the tables on first use */
 const half *cvs_lut_dev_or_null(int which);
+/* the table as the separate-arithmetic flavour builds it, whatever the call's flavour (cvs_lut_device follows the flavour:
+ * linear -> Rec.709 and linear -> sRGB differ between the two) */
+const half *cvs_lut_device_separate(int which);
 
 #endif

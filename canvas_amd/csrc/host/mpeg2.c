@@ -1,0 +1,67 @@
+/*
+ * mpeg2.c -- MPEG-2 4:2:0 edge of the path: half RGBA frame -> planar 8-bit Y'CbCr, interlaced chroma siting.
+ *
+ *   video_subsample_mpeg2 ... src/cprocess/video_subsample.c:189-526 (video_subsample_mpeg2_gl: GLSL only there)
+ * The reference fixes the raster at 720x480 with its origin at frame coordinate (0, 0); the device entry takes any
+ * width x height with width even and height a multiple of 4 (both fields of every chroma row pair inside the raster).
+ * What the kernel computes, rounding included, is stated in DESIGN.md "MPEG-2 4:2:0 subsample" and in
+ * kernels/mpeg2_ops.hip.  The caller's frame is only read.
+ */
+#include "internal.h"
+
+enum { MPEG2_W = 720, MPEG2_H = 480 };
+
+static bool mpeg2_size_ok(int width, int height) { return width >= 2 && !(width & 1) && height >= 4 && !(height & 3); }
+
+CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16 *frame, int width, int height, cvs_stream_t stream) {
+    if (cvs_enter() != 0) return -1;
+    if (!mpeg2_size_ok(width, height)) { cvs_set_error("MPEG-2 subsample: %dx%d: the width must be even and the height a multiple of 4", width, height); return -1; }
+    if (!planar || !frame || !planar->data[0] || !planar->data[1] || !planar->data[2]) { cvs_set_error("MPEG-2 subsample: need a frame and three planes"); return -1; }
+    if (planar->stride[0] < width || planar->stride[1] < width / 2 || planar->stride[2] < width / 2 ||
+        planar->line_count[0] < height || planar->line_count[1] < height / 2 || planar->line_count[2] < height / 2) {
+        cvs_set_error("MPEG-2 subsample: need planes of %dx%d, %dx%d, %dx%d", width, height, width / 2, height / 2, width / 2, height / 2);
+        return -1;
+    }
+    if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("MPEG-2 subsample: current window outside the buffer"); return -1; }
+    /* pixels outside the current window (and outside the raster) count as black: the kernel reads inside w only */
+    box2i w;
+    box2i_set(&w, max(0, frame->current_window.min.x), max(0, frame->current_window.min.y),
+              min(width - 1, frame->current_window.max.x), min(height - 1, frame->current_window.max.y));
+    const cvk_rect none = { 0, 0, -1, -1 };
+    const cvk_rect r = box2i_is_empty(&frame->current_window) || box2i_is_empty(&w) ? none : cvs_rect(&w);
+    /* the separate flavour's table in both flavours: the contracted build of linear -> Rec.709 fuses a * pow - b and differs at
+     * code 0x789b, and this filter's bytes must not depend on the flavour */
+    const half *lut = cvs_lut_device_separate(CVS_LUT_LINEAR_TO_REC709);
+    if (!lut) return -1;
+    cvk_dv_planes pl = { planar->data[0], planar->data[1], planar->data[2], planar->stride[0], planar->stride[1], planar->stride[2] };
+    CVS_KERNEL(cvk_mpeg2_subsample(&pl, cvs_view(frame->data, &frame->full_window), r, width, height, lut, cvs_cus(), cvs_pick_stream(stream)));
+    return 0;
+}
+
+/* ---- reference-named entry point on host memory: 720x480, planes allocated like video_subsample_dv's ---- */
+
+CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame) {
+    const int strides[3] = { MPEG2_W, MPEG2_W / 2, MPEG2_W / 2 }, lines[3] = { MPEG2_H, MPEG2_H / 2, MPEG2_H / 2 };
+    if (cvs_enter() != 0 || !frame) return NULL;
+    if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("MPEG-2 subsample: current window outside the buffer"); return NULL; }
+    coded_image *out = coded_image_alloc(strides, lines, 3);
+    if (!out) return NULL;
+    hipStream_t s = cvs_pick_stream(NULL);
+    size_t off[3], total = 0;
+    for (int p = 0; p < 3; p++) { off[p] = total; total += ((size_t)strides[p] * (size_t)lines[p] + 255) & ~(size_t)255; }
+    const bool have_pixels = !box2i_is_empty(&frame->current_window);
+    const size_t fbytes = have_pixels ? cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16) : 0;
+    rgba_frame_f16 dframe = *frame;
+    dframe.data = cvs_pool_malloc(fbytes ? fbytes : 1, s);
+    char *block = cvs_pool_malloc(total, s);
+    int rc = dframe.data && block ? 0 : -1;
+    if (rc == 0 && have_pixels) rc = cvs_memcpy_h2d(dframe.data, frame->data, fbytes, s);
+    coded_image dev = *out;
+    for (int p = 0; p < 3; p++) dev.data[p] = block ? block + off[p] : NULL;
+    if (rc == 0) rc = cvs_subsample_mpeg2_dev(&dev, &dframe, MPEG2_W, MPEG2_H, s);
+    for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_d2h(out->data[p], dev.data[p], (size_t)strides[p] * (size_t)lines[p], s);
+    cvs_pool_free(block, s);
+    cvs_pool_free(dframe.data, s);
+    if (rc != 0) { out->free_func(out); return NULL; }
+    return out;
+}

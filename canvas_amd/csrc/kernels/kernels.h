@@ -278,6 +278,13 @@ typedef struct { float coeff[16]; int width, center; } cvk_dv_taps;
 int cvk_dv_reconstruct(cvk_view frame, cvk_rect cur, const cvk_dv_planes *pl, const cvk_dv_taps *tri, const uint16_t *lut, void *stream);
 int cvk_dv_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, const cvk_dv_taps *tri, const uint16_t *lut, int encode_in_place, void *stream);
 
+/* MPEG-2 4:2:0 edge (video_subsample.c:189-526, DESIGN.md "MPEG-2 4:2:0 subsample"): Y' width x height, Cb and Cr
+ * width/2 x height/2 into the three planes of `pl`, every byte of those rasters written; `w` = the frame's current window
+ * clipped to the raster (may be empty: black planes).  width even >= 2, height a multiple of 4.  One arithmetic flavour
+ * (no FMA in either: the unit is not rebuilt with -DCVS_CONTRACT); `lut` = the separate flavour's linear -> Rec.709 half table
+ * (cvs_lut_device_separate) in both flavours. */
+int cvk_mpeg2_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int width, int height, const uint16_t *lut, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

@@ -1,13 +1,14 @@
 /*
- * pydv.c -- coded-image sources and the two DV 4:1:1 nodes.
+ * pydv.c -- coded-image sources, the two DV 4:1:1 nodes and the MPEG-2 4:2:0 node.
  *
  *   CodedImageSource, CodedImage, py_coded_image_take_source ... src/process/CodedImageSource.c:28-272,
  *                                                                include/pyframework.h:121-132
  *   DVReconstructionFilter(source)  coded images -> VideoSource   src/process/DVReconstructionFilter.c:31-110
  *   DVSubsampleFilter(source)       VideoSource -> coded images   src/process/DVSubsampleFilter.c:31-110
+ *   MPEG2SubsampleFilter(source, size=(720, 480))   VideoSource -> Y'CbCr 4:2:0   src/process/MPEG2SubsampleFilter.c (GL there)
  *
  * A coded image is a handful of byte planes in host memory (it is what a decoder hands over or an encoder
- * takes), so these two nodes are where bytes cross PCIe: the reconstruction node uploads three planes
+ * takes), so these nodes are where bytes cross PCIe: the reconstruction node uploads three planes
  * (518 400 bytes) and renders straight into the device frame it was given; the subsample node pulls its
  * source into a device frame, converts there and downloads the three planes.
  */
@@ -228,6 +229,70 @@ static PyTypeObject py_type_DVSubsampleFilter = {
     .tp_dealloc = (destructor)sub_dealloc, .tp_getset = sub_getset,
 };
 
+/* ---------------------------------------------------------------- MPEG2SubsampleFilter */
+
+/* src/process/MPEG2SubsampleFilter.c (GL-only in the reference, video_subsample_mpeg2_gl): the same node on the device
+ * entry, with the raster as a keyword (the reference's 720x480 by default).  Pull (0,0)-(W-1,H-1) into a device frame,
+ * subsample there, download Y' W x H and Cb, Cr W/2 x H/2. */
+typedef struct { PyObject_HEAD video_source *source; int width, height; } py_mpeg2sub;
+
+static int mpeg2_init(py_mpeg2sub *self, PyObject *args, PyObject *kw) {
+    static char *kwlist[] = { "source", "size", NULL };
+    PyObject *src, *size = NULL;
+    if (!PyArg_ParseTupleAndKeywords(args, kw, "O|O", kwlist, &src, &size)) return -1;
+    v2i sz = { 720, 480 };
+    if (size && !py_parse_v2i(size, &sz)) return -1;
+    if (sz.x < 2 || (sz.x & 1) || sz.y < 4 || (sz.y & 3)) {
+        PyErr_Format(PyExc_ValueError, "MPEG2SubsampleFilter: size (%d, %d): the width must be even and at least 2, the height a multiple of 4", sz.x, sz.y);
+        return -1;
+    }
+    if (!py_video_take_source(src, &self->source)) return -1;
+    self->width = sz.x;
+    self->height = sz.y;
+    return 0;
+}
+static void mpeg2_dealloc(py_mpeg2sub *self) {
+    py_video_take_source(NULL, &self->source);
+    Py_TYPE(self)->tp_free((PyObject *)self);
+}
+
+static coded_image *mpeg2_get_frame(py_mpeg2sub *self, int frame, int quality) {
+    const int w = self->width, h = self->height;
+    const int strides[3] = { w, w / 2, w / 2 }, lines[3] = { h, h / 2, h / 2 };
+    box2i window;
+    box2i_set(&window, 0, 0, w - 1, h - 1);
+    coded_image *out = coded_image_alloc(strides, lines, 3);
+    if (!out) return NULL;
+    rgba_frame_dev d = { NULL, CVS_FORMAT_F16, window, window, NULL };
+    size_t off[3], total = 0;
+    for (int p = 0; p < 3; p++) { off[p] = total; total += (((size_t)strides[p] * (size_t)lines[p]) + 255) & ~(size_t)255; }
+    d.data = cvs_pool_malloc(frame_bytes(&window, CVS_FORMAT_F16), NULL);
+    char *block = cvs_pool_malloc(total, NULL);
+    int rc = (d.data && block) ? 0 : -1;
+    if (rc == 0) {
+        video_get_frame_dev(self->source, frame, &d);
+        coded_image dev = *out;
+        for (int p = 0; p < 3; p++) dev.data[p] = block + off[p];
+        rgba_frame_f16 in = { d.data, d.full_window, d.current_window };
+        rc = cvs_subsample_mpeg2_dev(&dev, &in, w, h, NULL);
+        for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_d2h(out->data[p], dev.data[p], (size_t)strides[p] * (size_t)lines[p], NULL);
+    }
+    cvs_pool_free(block, NULL);
+    cvs_pool_free(d.data, NULL);
+    if (rc != 0) { out->free_func(out); return NULL; }
+    return out;
+}
+
+static coded_image_source_funcs mpeg2_funcs = { 0, (coded_image_getFrameFunc)mpeg2_get_frame };
+static PyObject *mpeg2_capsule;
+static PyGetSetDef mpeg2_getset[] = { { CODED_IMAGE_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Coded image source C API.", &mpeg2_capsule }, { NULL } };
+static PyTypeObject py_type_MPEG2SubsampleFilter = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    .tp_name = "fluggo.media.process.MPEG2SubsampleFilter", .tp_basicsize = sizeof(py_mpeg2sub), .tp_flags = Py_TPFLAGS_DEFAULT,
+    .tp_base = &py_type_CodedImageSource, .tp_new = PyType_GenericNew, .tp_init = (initproc)mpeg2_init,
+    .tp_dealloc = (destructor)mpeg2_dealloc, .tp_getset = mpeg2_getset,
+};
+
 int init_dv(PyObject *module) {
     PyObject *collections = PyImport_ImportModule("collections");
     if (!collections) return -1;
@@ -237,10 +302,12 @@ int init_dv(PyObject *module) {
     PyObject_SetAttrString(coded_image_tuple, "__module__", PyUnicode_FromString("fluggo.media.process"));
     cis_capsule = PyCapsule_New(&cis_funcs, CODED_IMAGE_SOURCE_FUNCS, NULL);
     sub_capsule = PyCapsule_New(&sub_funcs, CODED_IMAGE_SOURCE_FUNCS, NULL);
-    if (!cis_capsule || !sub_capsule || pyext_make_capsule(&recon_capsule, &recon_funcs) < 0) return -1;
+    mpeg2_capsule = PyCapsule_New(&mpeg2_funcs, CODED_IMAGE_SOURCE_FUNCS, NULL);
+    if (!cis_capsule || !sub_capsule || !mpeg2_capsule || pyext_make_capsule(&recon_capsule, &recon_funcs) < 0) return -1;
     Py_INCREF(coded_image_tuple);
     if (PyModule_AddObject(module, "CodedImage", coded_image_tuple) < 0) return -1;
     if (pyext_add_type(module, "CodedImageSource", &py_type_CodedImageSource) < 0) return -1;
     if (pyext_add_type(module, "DVReconstructionFilter", &py_type_DVReconstructionFilter) < 0) return -1;
-    return pyext_add_type(module, "DVSubsampleFilter", &py_type_DVSubsampleFilter);
+    if (pyext_add_type(module, "DVSubsampleFilter", &py_type_DVSubsampleFilter) < 0) return -1;
+    return pyext_add_type(module, "MPEG2SubsampleFilter", &py_type_MPEG2SubsampleFilter);
 }

@@ -366,6 +366,14 @@ CVS_EXPORT coded_image *video_subsample_dv(rgba_frame_f16 *frame);              
 /* device frame + device planes (planar->data[] are device pointers) */
 CVS_EXPORT int cvs_reconstruct_dv_dev(rgba_frame_f16 *frame, const coded_image *planar, cvs_stream_t stream);
 CVS_EXPORT int cvs_subsample_dv_dev(coded_image *planar, rgba_frame_f16 *frame, int encode_input_in_place, cvs_stream_t stream);
+/* MPEG-2 4:2:0 edge, interlaced chroma siting (video_subsample.c:189-526, video_subsample_mpeg2_gl: GLSL only in the reference;
+ * the contract, rounding included, is DESIGN.md "MPEG-2 4:2:0 subsample").  Planar 8-bit Y'CbCr: Y' width x height, Cb and Cr
+ * width/2 x height/2, raster origin at frame (0, 0); pixels outside the current window encode as black; Rec.601 matrix as the
+ * reference uses it (:405-410); the caller's frame is only read.  width even >= 2, height a multiple of 4 >= 4, else -1.
+ * video_subsample_mpeg2: host frame, the reference's 720x480, planes allocated as video_subsample_dv's; NULL on failure.
+ * cvs_subsample_mpeg2_dev: device planes (strides and line counts at least the raster's) and device frame; 0 on success. */
+CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame);
+CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16 *frame, int width, int height, cvs_stream_t stream);
 
 /* 2:3 pulldown removal (src/process/Pulldown23RemovalFilter.c:43-107; the reference keeps this inside the Python
  * node, the arithmetic and the field weave are entry points here so that the node is a thin caller).
