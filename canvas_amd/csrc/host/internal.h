@@ -5,6 +5,7 @@
 #define CVS_INTERNAL_H
 
 #include <hip/hip_runtime_api.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -110,5 +111,29 @@ const half *cvs_lut_dev_or_null(int which);
 /* the table as the separate-arithmetic flavour builds it, whatever the call's flavour (cvs_lut_device follows the flavour:
  * linear -> Rec.709 and linear -> sRGB differ between the two) */
 const half *cvs_lut_device_separate(int which);
+
+/* a * b + c where the reference's C has it in ONE expression (video_scale.c:65,257-277): rounded twice as its gcc build does,
+ * or once -- the fused multiply-add its clang build emits -- in the contracted flavour (canvas_hip.h cvs_set_arithmetic).
+ * The host C is compiled with -ffp-contract=off, so the first form never fuses by itself. */
+static inline float madd_as(int contracted, float a, float b, float c) { return contracted ? fmaf(a, b, c) : a * b + c; }
+
+/* ---- fir_tables.c: the separable FIR kernels' tap tables, one per axis, planned on the host and cached on the device per
+ * context.  A lookup returns 0 and the table PINNED: it stays on the device until cvs_fir_table_release() says the launch
+ * that reads it is on its stream (or hands the hold to the graph being captured there).  On failure pin is -1 and the error
+ * is set.  Target lines t0..t1 read source lines s0..s1; `tile`: the k_fir2d tile edge along this axis (max_foot's unit). */
+typedef struct {
+    cvk_fir_axis axis;
+    int max_foot;             /* most source lines any tile of the table reads */
+    int used_lo, used_hi;     /* target lines that receive at least one tap */
+    int pin;
+} cvs_fir_table;
+/* the blur: the same taps for every line, centre ntaps / 2 */
+int cvs_fir_table_blur(const float *taps, int ntaps, int t0, int t1, int s0, int s1, int tile, cvs_fir_table *out);
+/* the Lanczos resampler: per target line filter_createLanczos(factor, ksize, frac(t / factor)) */
+int cvs_fir_table_lanczos(float factor, int ksize, int t0, int t1, int s0, int s1, int tile, cvs_fir_table *out);
+/* one pass of video_scale_bilinear_f32 (video_scale.c:34-229) in the call's arithmetic flavour; count_touch: an in-range tap
+ * marks its target line as used even when the other axis is empty (the vertical pass).  Tile edge CVK_FIR2D_TILE_X. */
+int cvs_fir_table_triangle(float tmin, float smin, float factor, int s0, int s1, int t0, int t1, bool count_touch, cvs_fir_table *out);
+void cvs_fir_table_release(cvs_fir_table *t, hipStream_t s);
 
 #endif

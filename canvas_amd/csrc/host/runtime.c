@@ -14,7 +14,7 @@
 #include <time.h>
 
 /* ---- device contexts.  A context = one HIP device + everything the library keeps ON that device for its own use: the
- * scratch pool (below), the transfer tables (halfconv.c), the FIR tap tables (scale.c), the byte tables (display.c), and one
+ * scratch pool (below), the transfer tables (halfconv.c), the FIR tap tables (fir_tables.c), the byte tables (display.c), and one
  * stream per calling thread.  A process starts with none; cvs_init(device) -- or the first entry point, with CVS_DEVICE --
  * opens context 0 and makes it the DEFAULT: what every thread runs in that never chose another.  cvs_context_open(device)
  * opens further ones (another GPU of the node -- or the same one again: two contexts on one device share nothing but the

@@ -67,7 +67,7 @@ __device__ __forceinline__ void each_slot(F &f, std::integer_sequence<int, Js...
 // STEP > 1: the same sweep as a decimating resampler -- target line t reads source lines STEP*t - c + k.  That
 // is what the Lanczos gather degenerates to when the scale factor is 1/STEP with STEP a power of two: every
 // line centre t / factor is an integer, every fractional offset is 0, every line gets the same taps
-// (scale.c plan_lanczos).  A lane then loads STEP source columns per row, the LDS row is kept de-interleaved
+// (fir_tables.c plan_lanczos).  A lane then loads STEP source columns per row, the LDS row is kept de-interleaved
 // (one array per column phase, so tap reads stay contiguous across lanes), H is formed for target columns only,
 // every source row is pushed into the ring, and an output row leaves every STEP-th step.
 template <int NT, int W, bool INH, bool EPI, int STEP>

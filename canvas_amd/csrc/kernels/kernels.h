@@ -169,7 +169,7 @@ typedef struct {
 #define CVK_FIR_LREC 32
 /* One device block per table: ntaps | src | taps | foot | lrec, each part on a 256-byte boundary, ntaps first.  A kernel that
  * is handed the block's start can form the other pointers itself (tile_vh_ops.hip does, to have them before its arguments
- * arrive); the host lays the block out with the same macros (scale.c axis_upload). */
+ * arrive); the host lays the block out with the same macros (fir_tables.c axis_upload). */
 #define CVK_AXIS_ALIGN(bytes)              (((size_t)(bytes) + 255) & ~(size_t)255)
 #define CVK_AXIS_NLINES(lines)             ((size_t)((lines) > 0 ? (lines) : 1))
 #define CVK_AXIS_OFF_SRC(lines)            CVK_AXIS_ALIGN(CVK_AXIS_NLINES(lines) * 4)

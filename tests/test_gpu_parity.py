@@ -864,7 +864,7 @@ _FIR_SEEN = {}
 
 def ran_on(cvs, forced, fallback=None, note=None):
     """cvs_fir_last_kernel() after a launch pinned with force_fir(forced): the pinned kernel, or -- for a table pair that
-    kernel does not take -- the documented fallback named by the caller (host/scale.c fir2d_launch: hv -> tiled -> the two
+    kernel does not take -- the documented fallback named by the caller (host/scale.c fir_pair_launch: hv -> tiled -> the two
     passes; "passes" pins the last).  The per-line gather (hv) exists in the default arithmetic flavour only: in the contracted
     one a table pair goes to the tiles, or to the two passes when its footprint does not fit them -- same sums, and that is
     what the test then checks."""
