@@ -18,6 +18,7 @@ FIR_PATH_AUTO, FIR_PATH_PASSES, FIR_PATH_TILED, FIR_PATH_TABLES, FIR_PATH_HV, FI
 FIR_KERNEL_NONE, FIR_KERNEL_WINDOW, FIR_KERNEL_HALVE, _FIR_KERNEL_RETIRED_3, FIR_KERNEL_VH, FIR_KERNEL_TILED, _FIR_KERNEL_RETIRED_6, FIR_KERNEL_TWO_PASS, FIR_KERNEL_PASS, FIR_KERNEL_HV, FIR_KERNEL_WINDOW_PAIR, FIR_KERNEL_HALVE_PAIR, FIR_KERNEL_TILE_VH = range(13)
 ARITH_SEPARATE, ARITH_CONTRACTED = 0, 1          # cvs_set_arithmetic: the reference's gcc build / its clang (contracting) build
 LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_TO_REC709, LUT_LINEAR_TO_SRGB = -1, 0, 1, 2, 3
+YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
 class rgba_f32(C.Structure):
@@ -164,6 +165,8 @@ SIGNATURES = {
     "cvs_subsample_dv_dev": (C.c_int, [P(coded_image), _F16, C.c_int, _vp]),
     "video_subsample_mpeg2": (P(coded_image), [_F16]),
     "cvs_subsample_mpeg2_dev": (C.c_int, [P(coded_image), _F16, C.c_int, C.c_int, _vp]),
+    "video_reconstruct_mpeg2": (None, [_F16, P(coded_image)]),
+    "cvs_reconstruct_mpeg2_dev": (C.c_int, [_F16, P(coded_image), C.c_int, C.c_int, C.c_int, _vp]),
     "cvs_frame_to_bytes_dev": (C.c_int, [_vp, _F16, C.c_int, C.c_int, _vp]),
     "video_frame_to_bytes": (C.c_int, [_vp, _F16, C.c_int, C.c_int]),
     "cvs_frame_to_rgba8_intent_dev": (C.c_int, [_vp, _F16, C.c_int, C.c_float, _vp]),

@@ -1,11 +1,15 @@
 /*
- * mpeg2.c -- MPEG-2 4:2:0 edge of the path: half RGBA frame -> planar 8-bit Y'CbCr, interlaced chroma siting.
+ * mpeg2.c -- MPEG-2 4:2:0 edges of the path: half RGBA frame <-> planar 8-bit Y'CbCr.
  *
- *   video_subsample_mpeg2 ... src/cprocess/video_subsample.c:189-526 (video_subsample_mpeg2_gl: GLSL only there)
+ *   video_subsample_mpeg2 ..... src/cprocess/video_subsample.c:189-526 (video_subsample_mpeg2_gl: GLSL only there)
+ *   video_reconstruct_mpeg2 ... no reference code (src/cprocess/video_reconstruct.c knows DV only); the inverse edge, for the
+ *                               4:2:0 images the reference's decoder hands out (src/libav/AVVideoDecoder.c:75-97)
  * The reference fixes the raster at 720x480 with its origin at frame coordinate (0, 0); the device entry takes any
  * width x height with width even and height a multiple of 4 (both fields of every chroma row pair inside the raster).
  * What the kernel computes, rounding included, is stated in DESIGN.md "MPEG-2 4:2:0 subsample" and in
  * kernels/mpeg2_ops.hip.  The caller's frame is only read.
+ * The reconstruction takes interlaced or progressive siting and the Rec.601 or Rec.709 matrix (DESIGN.md "MPEG-2 4:2:0
+ * reconstruction", kernels/mpeg2_recon_ops.hip); it writes the frame's pixels inside the raster and nothing else.
  */
 #include "internal.h"
 
@@ -64,4 +68,83 @@ CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame) {
     cvs_pool_free(dframe.data, s);
     if (rc != 0) { out->free_func(out); return NULL; }
     return out;
+}
+
+/* ---- the import edge: planar Y'CbCr 4:2:0 -> half RGBA ---- */
+
+/* Y'CbCr -> R'G'B', row by row, as video_reconstruct.c:55-59 (Rec.601, Poynton p. 305) and :62-66 (Rec.709, p. 316) state them */
+static const float ycc_601[9] = { 1.0f, 0.0f, 1.402f, 1.0f, -0.344136f, -0.714136f, 1.0f, 1.772f, 0.0f };
+static const float ycc_709[9] = { 1.0f, 0.0f, 1.5748f, 1.0f, -0.187324f, -0.468124f, 1.0f, 1.8556f, 0.0f };
+
+static bool recon_size_ok(int width, int height, bool progressive) {
+    return width >= 2 && !(width & 1) && height >= 2 && !(height & 1) && (progressive || (height >= 4 && !(height & 3)));
+}
+
+CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_image *planar, int width, int height, int flags, cvs_stream_t stream) {
+    if (!frame) { cvs_set_error("MPEG-2 reconstruct: need a frame"); return -1; }
+    box2i_set_empty(&frame->current_window);
+    if (cvs_enter() != 0) return -1;
+    const bool progressive = (flags & CVS_YCC_PROGRESSIVE) != 0;
+    if (flags & ~(CVS_YCC_PROGRESSIVE | CVS_YCC_REC709)) { cvs_set_error("MPEG-2 reconstruct: unknown flags 0x%x", (unsigned)flags); return -1; }
+    if (!recon_size_ok(width, height, progressive)) {
+        cvs_set_error("MPEG-2 reconstruct: %dx%d: the width must be even and at least 2, the height %s", width, height,
+                      progressive ? "even and at least 2" : "a multiple of 4 and at least 4");
+        return -1;
+    }
+    if (!planar || !planar->data[0] || !planar->data[1] || !planar->data[2]) { cvs_set_error("MPEG-2 reconstruct: need three planes"); return -1; }
+    if (planar->stride[0] < width || planar->stride[1] < width / 2 || planar->stride[2] < width / 2 ||
+        planar->line_count[0] < height || planar->line_count[1] < height / 2 || planar->line_count[2] < height / 2) {
+        cvs_set_error("MPEG-2 reconstruct: need planes of %dx%d, %dx%d, %dx%d", width, height, width / 2, height / 2, width / 2, height / 2);
+        return -1;
+    }
+    box2i w;
+    box2i_set(&w, max(0, frame->full_window.min.x), max(0, frame->full_window.min.y), min(width - 1, frame->full_window.max.x),
+              min(height - 1, frame->full_window.max.y));
+    if (box2i_is_empty(&frame->full_window) || box2i_is_empty(&w)) return 0;
+    /* the separate flavour's table in both flavours: the pixels must not depend on the flavour (the two build this table alike
+     * today, the rule keeps it so) */
+    const half *lut = cvs_lut_device_separate(CVS_LUT_REC709_TO_LINEAR_SCENE);
+    if (!lut) return -1;
+    cvk_dv_planes pl = { planar->data[0], planar->data[1], planar->data[2], planar->stride[0], planar->stride[1], planar->stride[2] };
+    const int rc = cvk_mpeg2_reconstruct(cvs_view(frame->data, &frame->full_window), cvs_rect(&w), &pl, width, height, progressive,
+                                         (flags & CVS_YCC_REC709) ? ycc_709 : ycc_601, lut, cvs_cus(), cvs_pick_stream(stream));
+    if (rc != 0) { cvs_set_error("MPEG-2 reconstruct: %s", hipGetErrorString((hipError_t)rc)); return rc; }
+    frame->current_window = w;
+    return 0;
+}
+
+/* reference-named entry point on host memory: the reference's 720x480, interlaced, Rec.601; planes staged in one pooled block */
+CVS_EXPORT void video_reconstruct_mpeg2(rgba_frame_f16 *frame, coded_image *planar) {
+    if (!frame) return;
+    box2i_set_empty(&frame->current_window);
+    if (cvs_enter() != 0) return;
+    if (!planar || !planar->data[0] || !planar->data[1] || !planar->data[2]) { cvs_set_error("MPEG-2 reconstruct: need three planes"); return; }
+    hipStream_t s = cvs_pick_stream(NULL);
+    size_t off[3], bytes[3], total = 0;
+    for (int p = 0; p < 3; p++) {
+        bytes[p] = (size_t)max(planar->stride[p], 0) * (size_t)max(planar->line_count[p], 0);
+        off[p] = total;
+        total += (bytes[p] + 255) & ~(size_t)255;
+    }
+    const size_t fbytes = cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16);
+    rgba_frame_f16 dframe = *frame;
+    dframe.data = cvs_pool_malloc(fbytes ? fbytes : 1, s);
+    char *block = cvs_pool_malloc(total ? total : 1, s);
+    coded_image dev = *planar;
+    int rc = dframe.data && block ? 0 : -1;
+    for (int p = 0; p < 3; p++) dev.data[p] = block ? block + off[p] : NULL;
+    for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_h2d(dev.data[p], planar->data[p], bytes[p], s);
+    if (rc == 0) rc = cvs_reconstruct_mpeg2_dev(&dframe, &dev, MPEG2_W, MPEG2_H, 0, s);
+    /* pixels outside the current window keep what the caller's buffer held: only the written rows come back */
+    if (rc == 0 && !box2i_is_empty(&dframe.current_window)) {
+        const box2i *c = &dframe.current_window, *f = &frame->full_window;
+        const size_t pitch = (size_t)(f->max.x - f->min.x + 1) * sizeof(rgba_f16);
+        const size_t at = (size_t)(c->min.y - f->min.y) * pitch + (size_t)(c->min.x - f->min.x) * sizeof(rgba_f16);
+        rc = hipMemcpy2DAsync((char *)frame->data + at, pitch, (const char *)dframe.data + at, pitch, (size_t)(c->max.x - c->min.x + 1) * sizeof(rgba_f16),
+                              (size_t)(c->max.y - c->min.y + 1), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
+        if (rc != 0) cvs_set_error("MPEG-2 reconstruct: download failed");
+    }
+    if (rc == 0) frame->current_window = dframe.current_window;
+    cvs_pool_free(block, s);
+    cvs_pool_free(dframe.data, s);
 }

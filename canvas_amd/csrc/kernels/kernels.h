@@ -284,6 +284,13 @@ int cvk_dv_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, const 
  * (no FMA in either: the unit is not rebuilt with -DCVS_CONTRACT); `lut` = the separate flavour's linear -> Rec.709 half table
  * (cvs_lut_device_separate) in both flavours. */
 int cvk_mpeg2_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int width, int height, const uint16_t *lut, int cus, void *stream);
+/* MPEG-2 4:2:0 import edge (DESIGN.md "MPEG-2 4:2:0 reconstruction"): Y' width x height, Cb and Cr width/2 x height/2 from the
+ * three planes of `pl` into the pixels of `frame` inside `w` (the frame's full window clipped to the raster; may be empty), nothing
+ * else written.  width even >= 2; height a multiple of 4 (interlaced) or even (progressive), >= 2.  `mat`: the nine Y'CbCr -> R'G'B'
+ * coefficients row by row.  One arithmetic flavour (no FMA in either: the unit is not rebuilt with -DCVS_CONTRACT); `lut` = the
+ * separate flavour's Rec.709 -> linear (scene) half table (cvs_lut_device_separate) in both flavours. */
+int cvk_mpeg2_reconstruct(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, int width, int height, int progressive, const float mat[9],
+                          const uint16_t *lut, int cus, void *stream);
 
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT

@@ -6,6 +6,8 @@
  *   DVReconstructionFilter(source)  coded images -> VideoSource   src/process/DVReconstructionFilter.c:31-110
  *   DVSubsampleFilter(source)       VideoSource -> coded images   src/process/DVSubsampleFilter.c:31-110
  *   MPEG2SubsampleFilter(source, size=(720, 480))   VideoSource -> Y'CbCr 4:2:0   src/process/MPEG2SubsampleFilter.c (GL there)
+ *   MPEG2ReconstructionFilter(source, size=(720, 480), interlaced=True, matrix="601")   Y'CbCr 4:2:0 -> VideoSource
+ *                                   (no reference node: the inverse of the one above, for the 4:2:0 images decoders hand out)
  *
  * A coded image is a handful of byte planes in host memory (it is what a decoder hands over or an encoder
  * takes), so these nodes are where bytes cross PCIe: the reconstruction node uploads three planes
@@ -293,6 +295,84 @@ static PyTypeObject py_type_MPEG2SubsampleFilter = {
     .tp_dealloc = (destructor)mpeg2_dealloc, .tp_getset = mpeg2_getset,
 };
 
+/* ---------------------------------------------------------------- MPEG2ReconstructionFilter */
+
+/* coded planes -> half RGBA on the device entry (DESIGN.md "MPEG-2 4:2:0 reconstruction"): the raster, the siting and the matrix
+ * as keywords.  Renders like DVReconstructionFilter: one pooled upload block for the three planes, straight into the device slot;
+ * planes too small for the raster give an empty window (the entry refuses them before any read). */
+typedef struct { PyObject_HEAD CodedImageSourceHolder source; int width, height, flags; } py_mpeg2recon;
+
+static int mpeg2r_init(py_mpeg2recon *self, PyObject *args, PyObject *kw) {
+    static char *kwlist[] = { "source", "size", "interlaced", "matrix", NULL };
+    PyObject *src, *size = NULL, *matrix = NULL;
+    int interlaced = 1;
+    if (!PyArg_ParseTupleAndKeywords(args, kw, "O|OpO", kwlist, &src, &size, &interlaced, &matrix)) return -1;
+    v2i sz = { 720, 480 };
+    if (size && !py_parse_v2i(size, &sz)) return -1;
+    if (sz.x < 2 || (sz.x & 1) || sz.y < 2 || (sz.y & 1) || (interlaced && (sz.y < 4 || (sz.y & 3)))) {
+        PyErr_Format(PyExc_ValueError, "MPEG2ReconstructionFilter: size (%d, %d): the width must be even and at least 2, the height %s", sz.x, sz.y,
+                     interlaced ? "a multiple of 4 (interlaced)" : "even and at least 2");
+        return -1;
+    }
+    int flags = interlaced ? 0 : CVS_YCC_PROGRESSIVE;
+    if (matrix) {
+        const char *m = PyUnicode_Check(matrix) ? PyUnicode_AsUTF8(matrix) : NULL;
+        if (m && !strcmp(m, "709")) flags |= CVS_YCC_REC709;
+        else if (!m || strcmp(m, "601")) {
+            PyErr_Clear();
+            PyErr_Format(PyExc_ValueError, "MPEG2ReconstructionFilter: matrix must be \"601\" or \"709\", not %R", matrix);
+            return -1;
+        }
+    }
+    if (!py_coded_image_take_source(src, &self->source)) return -1;
+    self->width = sz.x;
+    self->height = sz.y;
+    self->flags = flags;
+    return 0;
+}
+static void mpeg2r_dealloc(py_mpeg2recon *self) {
+    py_coded_image_take_source(NULL, &self->source);
+    Py_TYPE(self)->tp_free((PyObject *)self);
+}
+
+static void mpeg2r_render(PyObject *o, int frame_index, rgba_frame_dev *f) {      /* native: f16 */
+    py_mpeg2recon *self = (py_mpeg2recon *)o;
+    box2i_set_empty(&f->current_window);
+    if (!self->source.source.obj || !self->source.source.funcs || !self->source.source.funcs->getFrame) return;
+    coded_image *image = self->source.source.funcs->getFrame(self->source.source.obj, frame_index, 0);
+    if (!image) return;
+    size_t off[3], bytes[3], total = 0;
+    bool ok = image->data[0] && image->data[1] && image->data[2];
+    for (int p = 0; ok && p < 3; p++) {
+        bytes[p] = (size_t)image->stride[p] * (size_t)image->line_count[p];
+        off[p] = total;
+        total += (bytes[p] + 255) & ~(size_t)255;
+    }
+    char *block = ok ? cvs_pool_malloc(total ? total : 1, f->stream) : NULL;
+    if (block) {
+        coded_image dev = *image;
+        for (int p = 0; ok && p < 3; p++) {
+            dev.data[p] = block + off[p];
+            ok = cvs_memcpy_h2d(dev.data[p], image->data[p], bytes[p], f->stream) == 0;
+        }
+        rgba_frame_f16 out = { f->data, f->full_window, f->full_window };
+        if (ok && cvs_reconstruct_mpeg2_dev(&out, &dev, self->width, self->height, self->flags, f->stream) == 0) f->current_window = out.current_window;
+        /* the host planes may be freed below: the uploads must have left them */
+        cvs_stream_sync(f->stream);
+        cvs_pool_free(block, f->stream);
+    }
+    if (image->free_func) image->free_func(image);
+}
+DEFINE_NODE_VTABLE(mpeg2r, CVS_FORMAT_F16, 1, 0)
+static void *mpeg2r_unused[] __attribute__((unused)) = { (void *)mpeg2r_slot_32 };
+static PyGetSetDef mpeg2r_getset[] = { { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &mpeg2r_capsule }, { NULL } };
+static PyTypeObject py_type_MPEG2ReconstructionFilter = {
+    PyVarObject_HEAD_INIT(NULL, 0)
+    .tp_name = "fluggo.media.process.MPEG2ReconstructionFilter", .tp_basicsize = sizeof(py_mpeg2recon), .tp_flags = Py_TPFLAGS_DEFAULT,
+    .tp_base = &py_type_VideoSource, .tp_new = PyType_GenericNew, .tp_init = (initproc)mpeg2r_init,
+    .tp_dealloc = (destructor)mpeg2r_dealloc, .tp_getset = mpeg2r_getset,
+};
+
 int init_dv(PyObject *module) {
     PyObject *collections = PyImport_ImportModule("collections");
     if (!collections) return -1;
@@ -303,11 +383,14 @@ int init_dv(PyObject *module) {
     cis_capsule = PyCapsule_New(&cis_funcs, CODED_IMAGE_SOURCE_FUNCS, NULL);
     sub_capsule = PyCapsule_New(&sub_funcs, CODED_IMAGE_SOURCE_FUNCS, NULL);
     mpeg2_capsule = PyCapsule_New(&mpeg2_funcs, CODED_IMAGE_SOURCE_FUNCS, NULL);
-    if (!cis_capsule || !sub_capsule || !mpeg2_capsule || pyext_make_capsule(&recon_capsule, &recon_funcs) < 0) return -1;
+    if (!cis_capsule || !sub_capsule || !mpeg2_capsule || pyext_make_capsule(&recon_capsule, &recon_funcs) < 0 ||
+        pyext_make_capsule(&mpeg2r_capsule, &mpeg2r_funcs) < 0)
+        return -1;
     Py_INCREF(coded_image_tuple);
     if (PyModule_AddObject(module, "CodedImage", coded_image_tuple) < 0) return -1;
     if (pyext_add_type(module, "CodedImageSource", &py_type_CodedImageSource) < 0) return -1;
     if (pyext_add_type(module, "DVReconstructionFilter", &py_type_DVReconstructionFilter) < 0) return -1;
     if (pyext_add_type(module, "DVSubsampleFilter", &py_type_DVSubsampleFilter) < 0) return -1;
-    return pyext_add_type(module, "MPEG2SubsampleFilter", &py_type_MPEG2SubsampleFilter);
+    if (pyext_add_type(module, "MPEG2SubsampleFilter", &py_type_MPEG2SubsampleFilter) < 0) return -1;
+    return pyext_add_type(module, "MPEG2ReconstructionFilter", &py_type_MPEG2ReconstructionFilter);
 }

@@ -374,6 +374,24 @@ CVS_EXPORT int cvs_subsample_dv_dev(coded_image *planar, rgba_frame_f16 *frame, 
  * cvs_subsample_mpeg2_dev: device planes (strides and line counts at least the raster's) and device frame; 0 on success. */
 CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame);
 CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16 *frame, int width, int height, cvs_stream_t stream);
+/* MPEG-2 4:2:0 import edge: planar 8-bit Y'CbCr -> half RGBA, the way in for the 4:2:0 images a decoder hands out (no reference
+ * code: its libav decoder produces them, src/libav/AVVideoDecoder.c:75-97, and nothing turns them into frames; the contract,
+ * rounding included, is DESIGN.md "MPEG-2 4:2:0 reconstruction").  Planes: Y' width x height, Cb and Cr width/2 x height/2;
+ * strides and line counts may exceed the raster.  The raster's origin is frame (0, 0): current_window = full_window clipped to
+ * [0, width-1] x [0, height-1], and only those pixels are written (those outside keep what they held); an empty intersection
+ * is not an error (0, empty window).  Per pixel: studio-range decode by correctly rounded division (video_reconstruct.c:32-39),
+ * chroma interpolated vertically by the siting in `flags` and horizontally between even-column samples, the matrix evaluated as
+ * video_reconstruct.c:114-122 does with every product and sum rounded on its own in both arithmetic flavours, truncation to
+ * half and the Rec.709 -> linear (scene) table over all four halfs (the separate flavour's table in both).
+ * flags: 0 = interlaced siting (the exact inverse of cvs_subsample_mpeg2_dev's) and the Rec.601 matrix (video_reconstruct.c:
+ * 55-59); CVS_YCC_PROGRESSIVE: MPEG-2 progressive / H.264 siting (chroma between luma rows 2c and 2c+1); CVS_YCC_REC709: the
+ * Rec.709 matrix (:62-66).  Interlaced needs width even >= 2 and height a multiple of 4 >= 4, progressive width even >= 2 and
+ * height even >= 2; other sizes, other flag bits, missing or short planes: cvs_set_error, -1 and an empty current_window.
+ * cvs_reconstruct_mpeg2_dev: device planes (planar->data[] are device pointers) and device frame; 0 on success.
+ * video_reconstruct_mpeg2: host frame and host planes, 720x480, interlaced, Rec.601; on failure an empty current_window. */
+enum { CVS_YCC_PROGRESSIVE = 1, CVS_YCC_REC709 = 2 };
+CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_image *planar, int width, int height, int flags, cvs_stream_t stream);
+CVS_EXPORT void video_reconstruct_mpeg2(rgba_frame_f16 *frame, coded_image *planar);
 
 /* 2:3 pulldown removal (src/process/Pulldown23RemovalFilter.c:43-107; the reference keeps this inside the Python
  * node, the arithmetic and the field weave are entry points here so that the node is a thin caller).
