@@ -292,6 +292,14 @@ int cvk_mpeg2_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int
 int cvk_mpeg2_reconstruct(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, int width, int height, int progressive, const float mat[9],
                           const uint16_t *lut, int cus, void *stream);
 
+/* Field conversions on f16 frames (field_ops.hip, DESIGN.md "Field conversions").  `w`: the rectangle written, inside `out` and
+ * -- field_to_frame, soften -- inside in_cur, the input's current window, itself inside `in`; interlace: inside `out` only, a
+ * pixel outside the providing input's current window is zero.  One arithmetic flavour: every product is by a power of two, so
+ * the contracted build would give the same bits (the unit is not rebuilt with -DCVS_CONTRACT). */
+int cvk_field_to_frame(cvk_view out, cvk_view in, cvk_rect w, cvk_rect in_cur, int field, int cus, void *stream);
+int cvk_soften_fields(cvk_view out, cvk_view in, cvk_rect w, cvk_rect in_cur, int cus, void *stream);
+int cvk_interlace_fields(cvk_view out, cvk_view even, cvk_view odd, cvk_rect w, cvk_rect even_cur, cvk_rect odd_cur, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

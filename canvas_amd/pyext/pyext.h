@@ -53,6 +53,14 @@ PyObject *pyext_capsule_getter(PyObject *self, void *closure);      /* closure =
 int pyext_add_type(PyObject *module, const char *name, PyTypeObject *type);
 int pyext_make_capsule(PyObject **slot, video_frame_source_funcs *funcs);
 
+/* a node with one upstream source (pysources.c): the struct every such type starts with, the `source` attribute's getter and
+ * setter and the set_source(source) method table; reader lock around any upstream pull, writer lock where the source changes */
+typedef struct { PyObject_HEAD pthread_rwlock_t lock; video_source *source; } node1;
+PyObject *node1_get_source(node1 *self, void *closure);
+PyObject *node1_set_source(node1 *self, PyObject *args);
+int node1_set_source_attr(node1 *self, PyObject *value, void *closure);
+extern PyMethodDef node1_methods[];
+
 /* frame objects (pyframes.c) */
 PyObject *py_RgbaFrameF16_new(box2i *full_window, rgba_frame_f16 **frame);
 PyObject *py_RgbaFrameF32_new(box2i *full_window, rgba_frame_f32 **frame);
@@ -66,6 +74,7 @@ int init_framefuncs(PyObject *module);
 int init_animation(PyObject *module);
 int init_dv(PyObject *module);
 int init_sources(PyObject *module);
+int init_fields(PyObject *module);
 int init_workspace(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */

@@ -91,16 +91,14 @@ static PyTypeObject py_type_Empty = {
     .tp_base = &py_type_VideoSource, .tp_new = PyType_GenericNew, .tp_getset = empty_getset,
 };
 
-/* ---------------------------------------------------------------- shared: a node with one upstream source */
+/* ---------------------------------------------------------------- shared: a node with one upstream source (pyext.h: node1) */
 
-typedef struct { PyObject_HEAD pthread_rwlock_t lock; video_source *source; } node1;
-
-static PyObject *node1_get_source(node1 *self, void *c) {
+PyObject *node1_get_source(node1 *self, void *c) {
     PyObject *o = self->source ? (PyObject *)self->source->obj : Py_None;
     Py_INCREF(o);
     return o;
 }
-static PyObject *node1_set_source(node1 *self, PyObject *args) {
+PyObject *node1_set_source(node1 *self, PyObject *args) {
     PyObject *src;
     if (!PyArg_ParseTuple(args, "O", &src)) return NULL;
     py_wrlock_nogil(&self->lock);
@@ -109,7 +107,7 @@ static PyObject *node1_set_source(node1 *self, PyObject *args) {
     if (!ok) return NULL;
     Py_RETURN_NONE;
 }
-static int node1_set_source_attr(node1 *self, PyObject *value, void *c) {
+int node1_set_source_attr(node1 *self, PyObject *value, void *c) {
     py_wrlock_nogil(&self->lock);
     bool ok = py_video_take_source(value, &self->source);
     pthread_rwlock_unlock(&self->lock);
@@ -169,7 +167,7 @@ static PyGetSetDef gain_getset[] = {
     { "offset", (getter)gain_get_offset, (setter)gain_set_offset, "Offset (number or frame function)." },
     { NULL }
 };
-static PyMethodDef node1_methods[] = {
+PyMethodDef node1_methods[] = {
     { "set_source", (PyCFunction)node1_set_source, METH_VARARGS, "set_source(source)" },
     { NULL }
 };

@@ -404,6 +404,43 @@ CVS_EXPORT void video_reconstruct_mpeg2(rgba_frame_f16 *frame, coded_image *plan
 CVS_EXPORT int cvs_pulldown23_frames(int offset, int frame_index, int *first, int *second);
 CVS_EXPORT int cvs_weave_fields_f16_dev(rgba_frame_f16 *frame, const rgba_frame_f16 *other, cvs_stream_t stream);
 
+/* Field conversions: between woven (interlaced) frames -- field 1 on the even rows, field 2 on the odd rows, upper field first
+ * (fluggo/editor/plugins/_source.py:125-126) -- and whole pictures.  No reference code (the design lists the conversions,
+ * docs/sphinx/feature-proposal/canvas.rst:283-303, and the editor names them, fluggo/editor/model/sources.py:536-542); the
+ * contract, rounding included, is DESIGN.md "Field conversions" and what follows.
+ * All three device entries: f16 device frames; 0 on success, -1 with a message in cvs_last_error on failure, and
+ * out->current_window is set on every path (empty on failure).  The inputs are only read; `out` may not share its buffer with an
+ * input; an input whose current_window lies outside its full_window is refused.  Windows are arbitrary (negative coordinates,
+ * full windows larger than current windows); pixels of `out` outside its new current_window keep what they held.  Row parity
+ * is that of the absolute coordinate: y & 1 in two's complement, so row -1 is odd.  All four channels are treated alike (alpha
+ * is filtered as a channel, nothing is premultiplied: what video_scale.c does).  Arithmetic is f32 on exactly widened halfs, the
+ * result truncated to half as everywhere (half.c:47-51).  Every product is by 0.5 or 0.25 and exact for every finite half, so
+ * CVS_ARITH_SEPARATE and CVS_ARITH_CONTRACTED give the same bits: these entries do not depend on cvs_set_arithmetic.
+ *
+ * cvs_field_to_frame_f16_dev: one field made into a whole picture (bob and discard-a-field deinterlacing).  field: 0 = the even
+ *   rows, 1 = the odd rows, anything else is an error.  current_window = out->full_window ∩ in->current_window.  Rows of it with
+ *   (y & 1) == field are copied code for code.  Every other row is made from rows y - 1 and y + 1 of `in`, each used if it lies
+ *   inside in->current_window (whether or not inside out->full_window): both -- t = upper * 0.5f; u = lower * 0.5f; r = t + u
+ *   (one rounding); one -- that row's codes; none (a one-row window of the other parity) -- four zero halfs.
+ * cvs_soften_fields_f16_dev: vertical [1/4, 1/2, 1/4], so that one-row detail of a progressive picture does not flicker at field
+ *   rate once the frame is shown interlaced (the design's "weave interlace").  Same window rule.  With a, b, c rows y - 1, y,
+ *   y + 1 of `in`: t = a * 0.25f; t = t + b * 0.5f; t = t + c * 0.25f (two roundings); a neighbour outside in->current_window is
+ *   replaced by row y itself.
+ * cvs_interlace_fields_f16_dev: two pictures woven into one frame (bob interlacing, 2:3 pulldown addition).  current_window =
+ *   out->full_window ∩ the bounding box of the inputs' non-empty current windows (empty when both are).  Even rows come from
+ *   `even`, odd rows from `odd`, code for code; a pixel outside the providing frame's current_window is four zero halfs.  `even`
+ *   and `odd` may be the same frame.  Unlike cvs_weave_fields_f16_dev nothing is asked of how the inputs were allocated and
+ *   there is no x = 0 addressing quirk.
+ * cvs_pulldown23_add_frames: host arithmetic, the inverse of cvs_pulldown23_frames: output frame `frame_index` of a 2:3 cadence
+ *   with phase `offset` (0..4) takes its even rows from source frame *even_source and its odd rows from *odd_source.  Returns 1
+ *   when the two differ, 0 when they are the same frame, -1 (nothing written) for an offset outside 0..4.  Cadence AA BB BC CD DD
+ *   (Pulldown23RemovalFilter.c:56-60): add0(i) = 4 * floor(i / 5) + ([0, 1, 1, 2, 3], [0, 1, 2, 3, 3])[i mod 5], and
+ *   add(offset, i) = add0(i + offset) - [0, 1, 2, 3, 3][offset]; negative frame indices continue the cadence backwards. */
+CVS_EXPORT int cvs_field_to_frame_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *in, int field, cvs_stream_t stream);
+CVS_EXPORT int cvs_soften_fields_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *in, cvs_stream_t stream);
+CVS_EXPORT int cvs_interlace_fields_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *even, const rgba_frame_f16 *odd, cvs_stream_t stream);
+CVS_EXPORT int cvs_pulldown23_add_frames(int offset, int frame_index, int *even_source, int *odd_source);
+
 /* Display / export edge: the current window of an f16 frame as 4 bytes per pixel, packed row by row.
  * pre_lut: a transfer table applied to all four halfs first (CVS_LUT_NONE for none); then a half->u8 ramp.
  *
