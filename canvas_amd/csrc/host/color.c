@@ -39,15 +39,12 @@ CVS_EXPORT int cvs_color_matrix_f16_to_dev(rgba_frame_f16 *out, const rgba_frame
 }
 
 static void host_color(rgba_frame_f16 *frame, const float m[9], int pre, int post) {
-    if (box2i_is_empty(&frame->current_window) || cvs_enter() != 0) return;
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d = { 0 };
-    rgba_frame_f16 f = *frame;
-    int rc = cvs_stage_in(&d, frame->data, cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16), 1, s);
-    f.data = d.dev;
-    if (rc == 0) rc = cvs_color_matrix_f16_dev(&f, m, pre, post, s);
-    if (rc == 0) cvs_stage_out(&d, frame->data, s);
-    cvs_stage_free(&d);
+    cvs_bridge br;
+    rgba_frame_f16 f;
+    if (box2i_is_empty(&frame->current_window) || cvs_bridge_open(&br) != 0) return;
+    CVS_BRIDGE_FRAME(&br, f, frame, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_CALL(&br, cvs_color_matrix_f16_dev, &f, m, pre, post);
+    cvs_bridge_close(&br, frame->data);
 }
 
 /* SMPTE-C RGB (Rec.709 transfer) -> linear XYZ; coefficients as color.c:115-118, column-major */

@@ -5,8 +5,9 @@
  *   video_reconstruct_dv .................... src/cprocess/video_reconstruct.c:50-137
  *   video_subsample_dv ...................... src/cprocess/video_subsample.c:99-187
  * The raster is fixed: 720x480, first line at y = -1 on the frame plane, chroma 180 samples per line.
- * Host entry points stage planes / frame rows to the device and back; the cvs_*_dev twins work on device
- * planes and device frames.  The triangle taps come from filter_createTriangle, exactly as the reference
+ * Host entry points take the frame and the planes (one pooled block, 480 lines each) through the bridge
+ * (bridge.c); the cvs_*_dev twins work on device planes and device frames.
+ * The triangle taps come from filter_createTriangle, exactly as the reference
  * asks for them (sub = 4 for reconstruction, 1/4 for subsampling), and travel as kernel arguments.
  */
 #include "internal.h"
@@ -49,15 +50,7 @@ static int dv_taps(float sub, cvk_dv_taps *t) {
     return 0;
 }
 
-static bool dv_planes_ok(const coded_image *p) {
-    return p && p->data[0] && p->data[1] && p->data[2] && p->stride[0] >= DV_W && p->stride[1] >= DV_W / DV_SUB && p->stride[2] >= DV_W / DV_SUB &&
-           p->line_count[0] >= DV_H && p->line_count[1] >= DV_H && p->line_count[2] >= DV_H;
-}
-
-static cvk_dv_planes dv_view(const coded_image *p) {
-    cvk_dv_planes v = { p->data[0], p->data[1], p->data[2], p->stride[0], p->stride[1], p->stride[2] };
-    return v;
-}
+static bool dv_planes_ok(const coded_image *p) { return cvs_planes_check(p, DV_W, DV_H, DV_W / DV_SUB, DV_H) == CVS_PLANES_OK; }
 
 /* frame and planes on the device */
 CVS_EXPORT int cvs_reconstruct_dv_dev(rgba_frame_f16 *frame, const coded_image *planar, cvs_stream_t stream) {
@@ -69,7 +62,7 @@ CVS_EXPORT int cvs_reconstruct_dv_dev(rgba_frame_f16 *frame, const coded_image *
     cvk_dv_taps tri;
     const half *lut = cvs_lut_device(CVS_LUT_REC709_TO_LINEAR_SCENE);
     if (dv_taps((float)DV_SUB, &tri) != 0 || !lut) { box2i_set_empty(&frame->current_window); return -1; }
-    cvk_dv_planes pl = dv_view(planar);
+    cvk_dv_planes pl = cvs_planes_view(planar);
     CVS_KERNEL(CVK(cvk_dv_reconstruct)(cvs_view(frame->data, &frame->full_window), cvs_rect(&frame->current_window), &pl, &tri, lut, cvs_pick_stream(stream)));
     return 0;
 }
@@ -89,68 +82,44 @@ CVS_EXPORT int cvs_subsample_dv_dev(coded_image *planar, rgba_frame_f16 *frame, 
     cvk_dv_taps tri;
     const half *lut = cvs_lut_device(CVS_LUT_LINEAR_TO_REC709);
     if (dv_taps(1.0f / (float)DV_SUB, &tri) != 0 || !lut) return -1;
-    cvk_dv_planes pl = dv_view(planar);
+    cvk_dv_planes pl = cvs_planes_view(planar);
     CVS_KERNEL(CVK(cvk_dv_subsample)(&pl, cvs_view(frame->data, &frame->full_window), cvs_rect(&w), &tri, lut, encode_input_in_place, s));
     return 0;
 }
 
 /* ---- reference-named entry points on host memory ---- */
 
-typedef struct { coded_image dev; void *block; } dev_planes;
-
-static int planes_to_device(dev_planes *d, const coded_image *host, bool upload, hipStream_t s) {
-    memset(d, 0, sizeof *d);
-    size_t off[3], total = 0;
-    for (int p = 0; p < 3; p++) { off[p] = total; total += ((size_t)host->stride[p] * DV_H + 255) & ~(size_t)255; }
-    d->block = cvs_pool_malloc(total, s);
-    if (!d->block) return -1;
-    for (int p = 0; p < 3; p++) {
-        d->dev.data[p] = (char *)d->block + off[p];
-        d->dev.stride[p] = host->stride[p];
-        d->dev.line_count[p] = DV_H;
-        if (upload && cvs_memcpy_h2d(d->dev.data[p], host->data[p], (size_t)host->stride[p] * DV_H, s) != 0) return -1;
-    }
-    return 0;
-}
+static const int dv_lines[3] = { DV_H, DV_H, DV_H };
 
 CVS_EXPORT void video_reconstruct_dv(rgba_frame_f16 *frame, coded_image *planar) {
-    if (cvs_enter() != 0 || !dv_planes_ok(planar)) { box2i_set_empty(&frame->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    dev_planes dp;
-    const size_t fbytes = cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16);
-    rgba_frame_f16 dframe = *frame;
-    dframe.data = cvs_pool_malloc(fbytes ? fbytes : 1, s);
-    int rc = dframe.data ? planes_to_device(&dp, planar, true, s) : -1;
-    if (rc == 0) rc = cvs_reconstruct_dv_dev(&dframe, &dp.dev, s);
-    /* pixels outside the current window are undefined: the whole buffer comes back in one copy */
-    if (rc == 0 && !box2i_is_empty(&dframe.current_window)) rc = cvs_memcpy_d2h(frame->data, dframe.data, fbytes, s);
+    cvs_bridge br;
+    rgba_frame_f16 dframe;
+    coded_image dev;
+    if (cvs_bridge_open(&br) != 0 || !dv_planes_ok(planar)) { box2i_set_empty(&frame->current_window); return; }
+    CVS_BRIDGE_FRAME(&br, dframe, frame, 0);
+    cvs_bridge_planes(&br, &dev, planar, dv_lines, true);
+    CVS_BRIDGE_CALL(&br, cvs_reconstruct_dv_dev, &dframe, &dev);
     frame->current_window = dframe.current_window;
-    if (rc != 0) box2i_set_empty(&frame->current_window);
-    cvs_pool_free(dframe.data, s);
-    if (dframe.data) cvs_pool_free(dp.block, s);
+    /* pixels outside the current window are undefined: the whole buffer comes back in one copy */
+    if (cvs_bridge_close(&br, box2i_is_empty(&dframe.current_window) ? NULL : frame->data) != 0) box2i_set_empty(&frame->current_window);
 }
 
 CVS_EXPORT coded_image *video_subsample_dv(rgba_frame_f16 *frame) {
-    const int strides[3] = { DV_W, DV_W / DV_SUB, DV_W / DV_SUB }, lines[3] = { DV_H, DV_H, DV_H };
-    if (cvs_enter() != 0) return NULL;
-    coded_image *out = coded_image_alloc(strides, lines, 3);
+    const int strides[3] = { DV_W, DV_W / DV_SUB, DV_W / DV_SUB };
+    cvs_bridge br;
+    rgba_frame_f16 dframe;
+    coded_image dev;
+    if (cvs_bridge_open(&br) != 0) return NULL;
+    coded_image *out = coded_image_alloc(strides, dv_lines, 3);
     if (!out) return NULL;
-    hipStream_t s = cvs_pick_stream(NULL);
-    dev_planes dp;
-    memset(&dp, 0, sizeof dp);
-    const size_t fbytes = cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16);
-    rgba_frame_f16 dframe = *frame;
-    dframe.data = cvs_pool_malloc(fbytes ? fbytes : 1, s);
+    /* a window that reaches outside the buffer is no window (no error) */
     const bool have_pixels = !box2i_is_empty(&frame->current_window) && cvs_box_contains(&frame->full_window, &frame->current_window);
-    int rc = dframe.data ? planes_to_device(&dp, out, false, s) : -1;
-    if (rc == 0 && have_pixels) rc = cvs_memcpy_h2d(dframe.data, frame->data, fbytes, s);
-    if (rc == 0 && !have_pixels) box2i_set_empty(&dframe.current_window);
-    if (rc == 0) rc = cvs_subsample_dv_dev(&dp.dev, &dframe, 1, s);
-    for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_d2h(out->data[p], dp.dev.data[p], (size_t)strides[p] * DV_H, s);
+    CVS_BRIDGE_FRAME(&br, dframe, frame, have_pixels ? CVS_BRIDGE_UPLOAD : 0);
+    if (!have_pixels) box2i_set_empty(&dframe.current_window);
+    cvs_bridge_planes(&br, &dev, out, dv_lines, false);
+    CVS_BRIDGE_CALL(&br, cvs_subsample_dv_dev, &dev, &dframe, 1);
+    cvs_bridge_planes_back(&br, out, &dev);
     /* the reference leaves the rows it read transfer-encoded in the caller's frame (video_subsample.c:144) */
-    if (rc == 0 && have_pixels) rc = cvs_memcpy_d2h(frame->data, dframe.data, fbytes, s);
-    cvs_pool_free(dframe.data, s);
-    cvs_pool_free(dp.block, s);
-    if (rc != 0) { coded_image_release(out); return NULL; }
+    if (cvs_bridge_close(&br, have_pixels ? frame->data : NULL) != 0) { coded_image_release(out); return NULL; }
     return out;
 }

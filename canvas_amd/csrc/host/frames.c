@@ -12,7 +12,7 @@
  *   src/cprocess/video_filter.c:27-39 + gl.c:584   gain/offset (GLSL only in the reference)
  *   src/process/SolidColorVideoSource.c:52-101     solid fill loops
  * Every entry exists twice: `cvs_*_dev` on frames already in HBM, and the reference-named one on
- * host frames, which stages the buffers through HBM around the same `_dev` call.
+ * host frames, which takes the buffers through HBM around the same `_dev` call (the bridge, bridge.c).
  */
 #include "internal.h"
 
@@ -190,119 +190,105 @@ CVS_EXPORT int cvs_fill_solid_f32_dev(rgba_frame_f32 *frame, const box2i *window
 
 /* ---------------------------------------------------------------- host-frame wrappers */
 
-#define F16_BYTES(f) (cvs_box_pixels(&(f)->full_window) * sizeof(rgba_f16))
-#define F32_BYTES(f) (cvs_box_pixels(&(f)->full_window) * sizeof(rgba_f32))
+/* an input goes up only when it has pixels */
+#define UP_IF_PIXELS(f) (box2i_is_empty(&(f)->current_window) ? 0 : CVS_BRIDGE_UPLOAD)
+/* the output comes back whole with the window the device call gave it, emptied when any step failed */
+#define CLOSE_INTO(br, out, dev_out)                                                             \
+    do {                                                                                         \
+        (out)->current_window = (dev_out).current_window;                                        \
+        if (cvs_bridge_close(br, (out)->data) != 0) box2i_set_empty(&(out)->current_window);     \
+    } while (0)
 
 CVS_EXPORT void video_copy_frame_f16(rgba_frame_f16 *out, rgba_frame_f16 *in) {
-    if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d_in = { 0 }, d_out = { 0 };
-    rgba_frame_f16 fi = *in, fo = *out;
-    int rc = cvs_stage_in(&d_in, in->data, F16_BYTES(in), !box2i_is_empty(&in->current_window), s);
-    if (rc == 0) rc = cvs_stage_in(&d_out, out->data, F16_BYTES(out), 1, s);
-    fi.data = d_in.dev; fo.data = d_out.dev;
-    if (rc == 0) rc = cvs_copy_frame_f16_dev(&fo, &fi, s);
-    if (rc == 0) rc = cvs_stage_out(&d_out, out->data, s);
-    out->current_window = fo.current_window;
-    if (rc != 0) box2i_set_empty(&out->current_window);
-    cvs_stage_free(&d_in); cvs_stage_free(&d_out);
+    cvs_bridge br;
+    rgba_frame_f16 fi, fo;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, fi, in, UP_IF_PIXELS(in));
+    CVS_BRIDGE_FRAME(&br, fo, out, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_CALL(&br, cvs_copy_frame_f16_dev, &fo, &fi);
+    CLOSE_INTO(&br, out, fo);
 }
 
 CVS_EXPORT void video_copy_frame_alpha_f32(rgba_frame_f32 *out, rgba_frame_f32 *in, float alpha) {
     if (out == in && clampf(alpha, 0.0f, 1.0f) == 1.0f) return;
-    if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d_in = { 0 }, d_out = { 0 };
-    rgba_frame_f32 fi = *in, fo = *out;
-    int rc = cvs_stage_in(&d_out, out->data, F32_BYTES(out), 1, s);
-    if (rc == 0 && in != out) rc = cvs_stage_in(&d_in, in->data, F32_BYTES(in), !box2i_is_empty(&in->current_window), s);
-    fo.data = d_out.dev;
-    fi.data = in == out ? d_out.dev : d_in.dev;
-    if (rc == 0) rc = cvs_copy_frame_alpha_f32_dev(&fo, &fi, alpha, s);
-    if (rc == 0) rc = cvs_stage_out(&d_out, out->data, s);
-    out->current_window = fo.current_window;
-    if (rc != 0) box2i_set_empty(&out->current_window);
-    cvs_stage_free(&d_in); cvs_stage_free(&d_out);
+    cvs_bridge br;
+    rgba_frame_f32 fi, fo;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, fo, out, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_FRAME(&br, fi, in, UP_IF_PIXELS(in));
+    CVS_BRIDGE_CALL(&br, cvs_copy_frame_alpha_f32_dev, &fo, &fi, alpha);
+    CLOSE_INTO(&br, out, fo);
 }
 
 /* framework.h:236 (declared there, defined nowhere in the reference): the in-place case of the copy above */
 CVS_EXPORT void video_attenuate_f32(rgba_frame_f32 *frame, float alpha) { video_copy_frame_alpha_f32(frame, frame, alpha); }
 
 CVS_EXPORT void video_mix_cross_f32(rgba_frame_f32 *out, rgba_frame_f32 *a, rgba_frame_f32 *b, float mix_b) {
-    if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d_out = { 0 }, d_a = { 0 }, d_b = { 0 };
-    rgba_frame_f32 fo = *out, fa = *a, fb = *b;
-    int rc = cvs_stage_in(&d_out, out->data, F32_BYTES(out), 1, s);
-    if (rc == 0 && a != out) rc = cvs_stage_in(&d_a, a->data, F32_BYTES(a), !box2i_is_empty(&a->current_window), s);
-    if (rc == 0 && b != out && b != a) rc = cvs_stage_in(&d_b, b->data, F32_BYTES(b), !box2i_is_empty(&b->current_window), s);
-    fo.data = d_out.dev;
-    fa.data = a == out ? d_out.dev : d_a.dev;
-    fb.data = b == out ? d_out.dev : (b == a ? fa.data : d_b.dev);
-    if (rc == 0) rc = cvs_mix_cross_f32_dev(&fo, &fa, &fb, mix_b, s);
-    if (rc == 0) rc = cvs_stage_out(&d_out, out->data, s);
-    out->current_window = fo.current_window;
-    if (rc != 0) box2i_set_empty(&out->current_window);
-    cvs_stage_free(&d_out); cvs_stage_free(&d_a); cvs_stage_free(&d_b);
+    cvs_bridge br;
+    rgba_frame_f32 fo, fa, fb;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, fo, out, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_FRAME(&br, fa, a, UP_IF_PIXELS(a));
+    CVS_BRIDGE_FRAME(&br, fb, b, UP_IF_PIXELS(b));
+    CVS_BRIDGE_CALL(&br, cvs_mix_cross_f32_dev, &fo, &fa, &fb, mix_b);
+    CLOSE_INTO(&br, out, fo);
 }
 
 CVS_EXPORT void video_mix_over_f32(rgba_frame_f32 *out, rgba_frame_f32 *b, float mix_b) {
-    if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d_out = { 0 }, d_b = { 0 };
-    rgba_frame_f32 fo = *out, fb = *b;
-    int rc = cvs_stage_in(&d_out, out->data, F32_BYTES(out), 1, s);
-    if (rc == 0) rc = cvs_stage_in(&d_b, b->data, F32_BYTES(b), !box2i_is_empty(&b->current_window), s);
-    fo.data = d_out.dev; fb.data = d_b.dev;
-    if (rc == 0) rc = cvs_mix_over_f32_dev(&fo, &fb, mix_b, s);
-    if (rc == 0) rc = cvs_stage_out(&d_out, out->data, s);
-    out->current_window = fo.current_window;
-    if (rc != 0) box2i_set_empty(&out->current_window);
-    cvs_stage_free(&d_out); cvs_stage_free(&d_b);
+    cvs_bridge br;
+    rgba_frame_f32 fo, fb;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, fo, out, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_FRAME(&br, fb, b, UP_IF_PIXELS(b));
+    CVS_BRIDGE_CALL(&br, cvs_mix_over_f32_dev, &fo, &fb, mix_b);
+    CLOSE_INTO(&br, out, fo);
 }
 
 CVS_EXPORT void video_filter_gain_offset_f16(rgba_frame_f16 *out, rgba_frame_f16 *in, float gain, float offset) {
-    if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d_in = { 0 }, d_out = { 0 };
-    rgba_frame_f16 fi = *in, fo = *out;
-    int rc = cvs_stage_in(&d_out, out->data, F16_BYTES(out), 1, s);
-    if (rc == 0 && in != out) rc = cvs_stage_in(&d_in, in->data, F16_BYTES(in), !box2i_is_empty(&in->current_window), s);
-    fo.data = d_out.dev;
-    fi.data = in == out ? d_out.dev : d_in.dev;
-    if (rc == 0) rc = cvs_gain_offset_f16_dev(&fo, &fi, gain, offset, s);
-    if (rc == 0) rc = cvs_stage_out(&d_out, out->data, s);
-    out->current_window = fo.current_window;
-    if (rc != 0) box2i_set_empty(&out->current_window);
-    cvs_stage_free(&d_in); cvs_stage_free(&d_out);
+    cvs_bridge br;
+    rgba_frame_f16 fi, fo;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, fo, out, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_FRAME(&br, fi, in, UP_IF_PIXELS(in));
+    CVS_BRIDGE_CALL(&br, cvs_gain_offset_f16_dev, &fo, &fi, gain, offset);
+    CLOSE_INTO(&br, out, fo);
 }
 
 CVS_EXPORT void video_fill_solid_f16(rgba_frame_f16 *frame, const box2i *window, const rgba_f32 *color) {
-    if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d = { 0 };
-    rgba_frame_f16 f = *frame;
-    int rc = cvs_stage_in(&d, frame->data, F16_BYTES(frame), 1, s);
-    f.data = d.dev;
-    if (rc == 0) rc = cvs_fill_solid_f16_dev(&f, window, color, s);
-    if (rc == 0) rc = cvs_stage_out(&d, frame->data, s);
-    frame->current_window = f.current_window;
-    if (rc != 0) box2i_set_empty(&frame->current_window);
-    cvs_stage_free(&d);
+    cvs_bridge br;
+    rgba_frame_f16 f;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, f, frame, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_CALL(&br, cvs_fill_solid_f16_dev, &f, window, color);
+    CLOSE_INTO(&br, frame, f);
 }
 
 CVS_EXPORT void video_fill_solid_f32(rgba_frame_f32 *frame, const box2i *window, const rgba_f32 *color) {
-    if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d = { 0 };
-    rgba_frame_f32 f = *frame;
-    int rc = cvs_stage_in(&d, frame->data, F32_BYTES(frame), 1, s);
-    f.data = d.dev;
-    if (rc == 0) rc = cvs_fill_solid_f32_dev(&f, window, color, s);
-    if (rc == 0) rc = cvs_stage_out(&d, frame->data, s);
-    frame->current_window = f.current_window;
-    if (rc != 0) box2i_set_empty(&frame->current_window);
-    cvs_stage_free(&d);
+    cvs_bridge br;
+    rgba_frame_f32 f;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, f, frame, CVS_BRIDGE_UPLOAD);
+    CVS_BRIDGE_CALL(&br, cvs_fill_solid_f32_dev, &f, window, color);
+    CLOSE_INTO(&br, frame, f);
+}
+
+/* what a pull through the other host slot ends with (main.c:43-71 narrow, :115-139 widen): both buffers up, the source's
+ * current_window converted on the device, the target back whole.  0 on success. */
+static int convert_host_frame(rgba_frame_f16 *h16, rgba_frame_f32 *h32, bool narrow) {
+    cvs_bridge br;
+    rgba_frame_f16 d16;
+    rgba_frame_f32 d32;
+    cvs_bridge_open(&br);
+    if (narrow) {
+        CVS_BRIDGE_FRAME(&br, d32, h32, CVS_BRIDGE_UPLOAD);
+        CVS_BRIDGE_FRAME(&br, d16, h16, CVS_BRIDGE_UPLOAD);
+        CVS_BRIDGE_CALL(&br, cvs_frame_f32_to_f16_dev, &d16, &d32);
+    } else {
+        CVS_BRIDGE_FRAME(&br, d16, h16, CVS_BRIDGE_UPLOAD);
+        CVS_BRIDGE_FRAME(&br, d32, h32, CVS_BRIDGE_UPLOAD);
+        CVS_BRIDGE_CALL(&br, cvs_frame_f16_to_f32_dev, &d32, &d16);
+    }
+    return cvs_bridge_close(&br, narrow ? (void *)h16->data : (void *)h32->data);
 }
 
 /* ---------------------------------------------------------------- pull dispatch (main.c) */
@@ -314,7 +300,7 @@ CVS_EXPORT void video_get_frame_f16(video_source *source, int frame_index, rgba_
         /* a source with a device slot and no f16 host slot: render in HBM as f16 (the node narrows there, the same
          * truncation main.c:43-71 would apply to its f32 output) and bring back 8 B per pixel once */
         if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return; }
-        size_t bytes = F16_BYTES(frame);
+        size_t bytes = cvs_frame_bytes(&frame->full_window, sizeof(rgba_f16));
         rgba_frame_dev d = { cvs_pool_malloc(bytes, NULL), CVS_FORMAT_F16, frame->full_window, frame->full_window, NULL };
         if (!d.data) { box2i_set_empty(&frame->current_window); return; }
         source->funcs->get_frame_dev(source->obj, frame_index, &d);
@@ -332,23 +318,7 @@ CVS_EXPORT void video_get_frame_f16(video_source *source, int frame_index, rgba_
         tmp.full_window = frame->full_window;
         tmp.current_window = frame->full_window;
         source->funcs->get_frame_32(source->obj, frame_index, &tmp);
-        if (!box2i_is_empty(&tmp.current_window)) {
-            if (cvs_enter() == 0) {
-                hipStream_t s = cvs_pick_stream(NULL);
-                cvs_staged d32 = { 0 }, d16 = { 0 };
-                rgba_frame_f32 f32 = tmp;
-                rgba_frame_f16 f16 = *frame;
-                int rc = cvs_stage_in(&d32, tmp.data, n * sizeof(rgba_f32), 1, s);
-                if (rc == 0) rc = cvs_stage_in(&d16, frame->data, n * sizeof(rgba_f16), 1, s);
-                f32.data = d32.dev; f16.data = d16.dev;
-                if (rc == 0) rc = cvs_frame_f32_to_f16_dev(&f16, &f32, s);
-                if (rc == 0) rc = cvs_stage_out(&d16, frame->data, s);
-                if (rc != 0) box2i_set_empty(&tmp.current_window);
-                cvs_stage_free(&d32); cvs_stage_free(&d16);
-            } else {
-                box2i_set_empty(&tmp.current_window);
-            }
-        }
+        if (!box2i_is_empty(&tmp.current_window) && convert_host_frame(frame, &tmp, true) != 0) box2i_set_empty(&tmp.current_window);
         frame->current_window = tmp.current_window;
         free(tmp.data);
         return;
@@ -361,7 +331,7 @@ CVS_EXPORT void video_get_frame_f32(video_source *source, int frame_index, rgba_
     if (source->funcs->get_frame_32) { source->funcs->get_frame_32(source->obj, frame_index, frame); return; }
     if ((source->funcs->flags & VIDEO_SOURCE_FLAG_DEVICE) && source->funcs->get_frame_dev) {
         if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return; }
-        size_t bytes = F32_BYTES(frame);
+        size_t bytes = cvs_frame_bytes(&frame->full_window, sizeof(rgba_f32));
         rgba_frame_dev d = { cvs_pool_malloc(bytes, NULL), CVS_FORMAT_F32, frame->full_window, frame->full_window, NULL };
         if (!d.data) { box2i_set_empty(&frame->current_window); return; }
         source->funcs->get_frame_dev(source->obj, frame_index, &d);
@@ -378,23 +348,7 @@ CVS_EXPORT void video_get_frame_f32(video_source *source, int frame_index, rgba_
         tmp.full_window = frame->full_window;
         tmp.current_window = frame->full_window;
         source->funcs->get_frame(source->obj, frame_index, &tmp);
-        if (!box2i_is_empty(&tmp.current_window)) {
-            if (cvs_enter() == 0) {
-                hipStream_t s = cvs_pick_stream(NULL);
-                cvs_staged d32 = { 0 }, d16 = { 0 };
-                rgba_frame_f32 f32 = *frame;
-                rgba_frame_f16 f16 = tmp;
-                int rc = cvs_stage_in(&d16, tmp.data, n * sizeof(rgba_f16), 1, s);
-                if (rc == 0) rc = cvs_stage_in(&d32, frame->data, n * sizeof(rgba_f32), 1, s);
-                f32.data = d32.dev; f16.data = d16.dev;
-                if (rc == 0) rc = cvs_frame_f16_to_f32_dev(&f32, &f16, s);
-                if (rc == 0) rc = cvs_stage_out(&d32, frame->data, s);
-                if (rc != 0) box2i_set_empty(&tmp.current_window);
-                cvs_stage_free(&d32); cvs_stage_free(&d16);
-            } else {
-                box2i_set_empty(&tmp.current_window);
-            }
-        }
+        if (!box2i_is_empty(&tmp.current_window) && convert_host_frame(&tmp, frame, false) != 0) box2i_set_empty(&tmp.current_window);
         frame->current_window = tmp.current_window;
         free(tmp.data);
         return;

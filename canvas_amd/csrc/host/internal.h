@@ -95,9 +95,9 @@ static inline bool cvs_box_contains(const box2i *outer, const box2i *inner) {
         }                                                                                                  \
     } while (0)
 
-/* ---- staging of host frames for the reference-named entry points (H2D -> kernels -> D2H) */
+/* ---- staging of one flat host array (halfconv.c, display.c; the bridge below is built on it): H2D -> kernels -> D2H */
 typedef struct {
-    void *dev;            /* device copy of the whole full_window buffer (from the stream-ordered pool) */
+    void *dev;            /* device copy of the whole buffer (from the stream-ordered pool); NULL for a zero-byte one */
     size_t bytes;
     hipStream_t stream;   /* the stream it was staged on: the block goes back to the pool on it */
 } cvs_staged;
@@ -105,6 +105,54 @@ typedef struct {
 int cvs_stage_in(cvs_staged *st, const void *host, size_t bytes, int upload, hipStream_t s);
 int cvs_stage_out(cvs_staged *st, void *host, hipStream_t s);      /* D2H + sync */
 void cvs_stage_free(cvs_staged *st);
+
+/* ---- bridge.c: what every reference-named entry point on host frames does around its `_dev` twin.  Open, add the frames
+ * (and coded planes) the call touches, run the twin, close.  The first step that fails is kept in `rc` and every later step
+ * is skipped, so a caller never tracks which blocks exist; close frees them all, whatever happened.
+ *     cvs_bridge br;  rgba_frame_f32 fo, fb;
+ *     cvs_bridge_open(&br);
+ *     CVS_BRIDGE_FRAME(&br, fo, out, CVS_BRIDGE_UPLOAD);
+ *     CVS_BRIDGE_FRAME(&br, fb, b, box2i_is_empty(&b->current_window) ? 0 : CVS_BRIDGE_UPLOAD);
+ *     CVS_BRIDGE_CALL(&br, cvs_mix_over_f32_dev, &fo, &fb, mix_b);
+ *     out->current_window = fo.current_window;
+ *     if (cvs_bridge_close(&br, out->data) != 0) box2i_set_empty(&out->current_window);                                  */
+enum {
+    CVS_BRIDGE_UPLOAD = 1,       /* the host bytes go up (once per block) */
+    CVS_BRIDGE_PRIVATE = 2,      /* never the block of an earlier frame: for a twin that may not run in place */
+    CVS_BRIDGE_BLOCKS = 4
+};
+typedef struct {
+    hipStream_t stream;
+    int rc, n;
+    struct { const void *host; int uploaded; cvs_staged st; } blk[CVS_BRIDGE_BLOCKS];
+} cvs_bridge;
+
+int cvs_bridge_open(cvs_bridge *b);      /* cvs_enter + the thread's stream; the result is also b->rc */
+/* device copy of a host buffer, NULL for a zero-byte one: the same buffer (pointer and size) added twice is one block */
+void *cvs_bridge_frame(cvs_bridge *b, const void *host, size_t bytes, int flags);
+/* three coded planes in one block, each on a 256-byte boundary: lines[p] rows of host->stride[p] bytes, uploaded or not.
+ * *dev is *host with the device pointers and those line counts; _back downloads what *dev describes into host's planes */
+void cvs_bridge_planes(cvs_bridge *b, coded_image *dev, const coded_image *host, const int lines[3], bool upload);
+void cvs_bridge_planes_back(cvs_bridge *b, coded_image *host, const coded_image *dev);
+/* rows and columns `window` of the added buffer `host` (px bytes per pixel, covering `full`) come back; then a wait */
+int cvs_bridge_pull_window(cvs_bridge *b, void *host, const box2i *full, const box2i *window, size_t px);
+/* the added buffer `out_host` comes back whole, then a wait (NULL: neither); every block is freed; returns rc */
+int cvs_bridge_close(cvs_bridge *b, void *out_host);
+
+static inline size_t cvs_frame_bytes(const box2i *full, size_t px) { return cvs_box_pixels(full) * px; }
+/* dst = the device twin of host frame *src (either format): the same windows, the data pointer from the bridge */
+#define CVS_BRIDGE_FRAME(b, dst, src, flags)                                                                                  \
+    do { (dst) = *(src); (dst).data = cvs_bridge_frame(b, (src)->data, cvs_frame_bytes(&(src)->full_window, sizeof *(src)->data), flags); } while (0)
+/* fn(args..., the bridge's stream) unless an earlier step failed */
+#define CVS_BRIDGE_CALL(b, fn, ...) do { if ((b)->rc == 0) (b)->rc = fn(__VA_ARGS__, (b)->stream); } while (0)
+
+/* coded planes of a w x h luma raster with cw x ch chroma: which of the two things an entry asks of them fails first */
+enum { CVS_PLANES_OK = 0, CVS_PLANES_MISSING, CVS_PLANES_SMALL };
+int cvs_planes_check(const coded_image *image, int w, int h, int cw, int ch);
+static inline cvk_dv_planes cvs_planes_view(const coded_image *p) {
+    cvk_dv_planes v = { p->data[0], p->data[1], p->data[2], p->stride[0], p->stride[1], p->stride[2] };
+    return v;
+}
 
 /* device LUT for an id, NULL for CVS_LUT_NONE; builds the tables on first use */
 const half *cvs_lut_dev_or_null(int which);

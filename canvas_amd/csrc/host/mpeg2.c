@@ -7,7 +7,8 @@
  * The reference fixes the raster at 720x480 with its origin at frame coordinate (0, 0); the device entry takes any
  * width x height with width even and height a multiple of 4 (both fields of every chroma row pair inside the raster).
  * What the kernel computes, rounding included, is stated in DESIGN.md "MPEG-2 4:2:0 subsample" and in
- * kernels/mpeg2_ops.hip.  The caller's frame is only read.
+ * kernels/mpeg2_ops.hip.  The caller's frame is only read.  The reference-named entries take the frame and the planes (one
+ * pooled block) through the bridge (bridge.c).
  * The reconstruction takes interlaced or progressive siting and the Rec.601 or Rec.709 matrix (DESIGN.md "MPEG-2 4:2:0
  * reconstruction", kernels/mpeg2_recon_ops.hip); it writes the frame's pixels inside the raster and nothing else.
  */
@@ -20,9 +21,9 @@ static bool mpeg2_size_ok(int width, int height) { return width >= 2 && !(width 
 CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16 *frame, int width, int height, cvs_stream_t stream) {
     if (cvs_enter() != 0) return -1;
     if (!mpeg2_size_ok(width, height)) { cvs_set_error("MPEG-2 subsample: %dx%d: the width must be even and the height a multiple of 4", width, height); return -1; }
-    if (!planar || !frame || !planar->data[0] || !planar->data[1] || !planar->data[2]) { cvs_set_error("MPEG-2 subsample: need a frame and three planes"); return -1; }
-    if (planar->stride[0] < width || planar->stride[1] < width / 2 || planar->stride[2] < width / 2 ||
-        planar->line_count[0] < height || planar->line_count[1] < height / 2 || planar->line_count[2] < height / 2) {
+    const int planes = cvs_planes_check(planar, width, height, width / 2, height / 2);
+    if (!frame || planes == CVS_PLANES_MISSING) { cvs_set_error("MPEG-2 subsample: need a frame and three planes"); return -1; }
+    if (planes != CVS_PLANES_OK) {
         cvs_set_error("MPEG-2 subsample: need planes of %dx%d, %dx%d, %dx%d", width, height, width / 2, height / 2, width / 2, height / 2);
         return -1;
     }
@@ -37,7 +38,7 @@ CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16
      * code 0x789b, and this filter's bytes must not depend on the flavour */
     const half *lut = cvs_lut_device_separate(CVS_LUT_LINEAR_TO_REC709);
     if (!lut) return -1;
-    cvk_dv_planes pl = { planar->data[0], planar->data[1], planar->data[2], planar->stride[0], planar->stride[1], planar->stride[2] };
+    cvk_dv_planes pl = cvs_planes_view(planar);
     CVS_KERNEL(cvk_mpeg2_subsample(&pl, cvs_view(frame->data, &frame->full_window), r, width, height, lut, cvs_cus(), cvs_pick_stream(stream)));
     return 0;
 }
@@ -46,27 +47,21 @@ CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16
 
 CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame) {
     const int strides[3] = { MPEG2_W, MPEG2_W / 2, MPEG2_W / 2 }, lines[3] = { MPEG2_H, MPEG2_H / 2, MPEG2_H / 2 };
-    if (cvs_enter() != 0 || !frame) return NULL;
+    cvs_bridge br;
+    rgba_frame_f16 dframe;
+    coded_image dev;
+    if (cvs_bridge_open(&br) != 0 || !frame) return NULL;
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("MPEG-2 subsample: current window outside the buffer"); return NULL; }
     coded_image *out = coded_image_alloc(strides, lines, 3);
     if (!out) return NULL;
-    hipStream_t s = cvs_pick_stream(NULL);
-    size_t off[3], total = 0;
-    for (int p = 0; p < 3; p++) { off[p] = total; total += ((size_t)strides[p] * (size_t)lines[p] + 255) & ~(size_t)255; }
+    /* a frame without pixels is not read: one byte stands in for its buffer */
     const bool have_pixels = !box2i_is_empty(&frame->current_window);
-    const size_t fbytes = have_pixels ? cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16) : 0;
-    rgba_frame_f16 dframe = *frame;
-    dframe.data = cvs_pool_malloc(fbytes ? fbytes : 1, s);
-    char *block = cvs_pool_malloc(total, s);
-    int rc = dframe.data && block ? 0 : -1;
-    if (rc == 0 && have_pixels) rc = cvs_memcpy_h2d(dframe.data, frame->data, fbytes, s);
-    coded_image dev = *out;
-    for (int p = 0; p < 3; p++) dev.data[p] = block ? block + off[p] : NULL;
-    if (rc == 0) rc = cvs_subsample_mpeg2_dev(&dev, &dframe, MPEG2_W, MPEG2_H, s);
-    for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_d2h(out->data[p], dev.data[p], (size_t)strides[p] * (size_t)lines[p], s);
-    cvs_pool_free(block, s);
-    cvs_pool_free(dframe.data, s);
-    if (rc != 0) { out->free_func(out); return NULL; }
+    dframe = *frame;
+    dframe.data = cvs_bridge_frame(&br, frame->data, have_pixels ? cvs_frame_bytes(&frame->full_window, sizeof(rgba_f16)) : 1, have_pixels ? CVS_BRIDGE_UPLOAD : 0);
+    cvs_bridge_planes(&br, &dev, out, lines, false);
+    CVS_BRIDGE_CALL(&br, cvs_subsample_mpeg2_dev, &dev, &dframe, MPEG2_W, MPEG2_H);
+    cvs_bridge_planes_back(&br, out, &dev);
+    if (cvs_bridge_close(&br, NULL) != 0) { out->free_func(out); return NULL; }
     return out;
 }
 
@@ -91,9 +86,9 @@ CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_imag
                       progressive ? "even and at least 2" : "a multiple of 4 and at least 4");
         return -1;
     }
-    if (!planar || !planar->data[0] || !planar->data[1] || !planar->data[2]) { cvs_set_error("MPEG-2 reconstruct: need three planes"); return -1; }
-    if (planar->stride[0] < width || planar->stride[1] < width / 2 || planar->stride[2] < width / 2 ||
-        planar->line_count[0] < height || planar->line_count[1] < height / 2 || planar->line_count[2] < height / 2) {
+    const int planes = cvs_planes_check(planar, width, height, width / 2, height / 2);
+    if (planes == CVS_PLANES_MISSING) { cvs_set_error("MPEG-2 reconstruct: need three planes"); return -1; }
+    if (planes != CVS_PLANES_OK) {
         cvs_set_error("MPEG-2 reconstruct: need planes of %dx%d, %dx%d, %dx%d", width, height, width / 2, height / 2, width / 2, height / 2);
         return -1;
     }
@@ -105,7 +100,7 @@ CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_imag
      * today, the rule keeps it so) */
     const half *lut = cvs_lut_device_separate(CVS_LUT_REC709_TO_LINEAR_SCENE);
     if (!lut) return -1;
-    cvk_dv_planes pl = { planar->data[0], planar->data[1], planar->data[2], planar->stride[0], planar->stride[1], planar->stride[2] };
+    cvk_dv_planes pl = cvs_planes_view(planar);
     const int rc = cvk_mpeg2_reconstruct(cvs_view(frame->data, &frame->full_window), cvs_rect(&w), &pl, width, height, progressive,
                                          (flags & CVS_YCC_REC709) ? ycc_709 : ycc_601, lut, cvs_cus(), cvs_pick_stream(stream));
     if (rc != 0) { cvs_set_error("MPEG-2 reconstruct: %s", hipGetErrorString((hipError_t)rc)); return rc; }
@@ -115,36 +110,19 @@ CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_imag
 
 /* reference-named entry point on host memory: the reference's 720x480, interlaced, Rec.601; planes staged in one pooled block */
 CVS_EXPORT void video_reconstruct_mpeg2(rgba_frame_f16 *frame, coded_image *planar) {
+    cvs_bridge br;
+    rgba_frame_f16 dframe;
+    coded_image dev;
     if (!frame) return;
     box2i_set_empty(&frame->current_window);
-    if (cvs_enter() != 0) return;
-    if (!planar || !planar->data[0] || !planar->data[1] || !planar->data[2]) { cvs_set_error("MPEG-2 reconstruct: need three planes"); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    size_t off[3], bytes[3], total = 0;
-    for (int p = 0; p < 3; p++) {
-        bytes[p] = (size_t)max(planar->stride[p], 0) * (size_t)max(planar->line_count[p], 0);
-        off[p] = total;
-        total += (bytes[p] + 255) & ~(size_t)255;
-    }
-    const size_t fbytes = cvs_box_pixels(&frame->full_window) * sizeof(rgba_f16);
-    rgba_frame_f16 dframe = *frame;
-    dframe.data = cvs_pool_malloc(fbytes ? fbytes : 1, s);
-    char *block = cvs_pool_malloc(total ? total : 1, s);
-    coded_image dev = *planar;
-    int rc = dframe.data && block ? 0 : -1;
-    for (int p = 0; p < 3; p++) dev.data[p] = block ? block + off[p] : NULL;
-    for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_h2d(dev.data[p], planar->data[p], bytes[p], s);
-    if (rc == 0) rc = cvs_reconstruct_mpeg2_dev(&dframe, &dev, MPEG2_W, MPEG2_H, 0, s);
+    if (cvs_bridge_open(&br) != 0) return;
+    if (cvs_planes_check(planar, 0, 0, 0, 0) == CVS_PLANES_MISSING) { cvs_set_error("MPEG-2 reconstruct: need three planes"); return; }
+    CVS_BRIDGE_FRAME(&br, dframe, frame, 0);
+    cvs_bridge_planes(&br, &dev, planar, planar->line_count, true);
+    CVS_BRIDGE_CALL(&br, cvs_reconstruct_mpeg2_dev, &dframe, &dev, MPEG2_W, MPEG2_H, 0);
     /* pixels outside the current window keep what the caller's buffer held: only the written rows come back */
-    if (rc == 0 && !box2i_is_empty(&dframe.current_window)) {
-        const box2i *c = &dframe.current_window, *f = &frame->full_window;
-        const size_t pitch = (size_t)(f->max.x - f->min.x + 1) * sizeof(rgba_f16);
-        const size_t at = (size_t)(c->min.y - f->min.y) * pitch + (size_t)(c->min.x - f->min.x) * sizeof(rgba_f16);
-        rc = hipMemcpy2DAsync((char *)frame->data + at, pitch, (const char *)dframe.data + at, pitch, (size_t)(c->max.x - c->min.x + 1) * sizeof(rgba_f16),
-                              (size_t)(c->max.y - c->min.y + 1), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
-        if (rc != 0) cvs_set_error("MPEG-2 reconstruct: download failed");
-    }
-    if (rc == 0) frame->current_window = dframe.current_window;
-    cvs_pool_free(block, s);
-    cvs_pool_free(dframe.data, s);
+    if (br.rc == 0 && !box2i_is_empty(&dframe.current_window) &&
+        cvs_bridge_pull_window(&br, frame->data, &frame->full_window, &dframe.current_window, sizeof(rgba_f16)) != 0)
+        cvs_set_error("MPEG-2 reconstruct: download failed");
+    if (cvs_bridge_close(&br, NULL) == 0) frame->current_window = dframe.current_window;
 }

@@ -414,18 +414,15 @@ CVS_EXPORT int cvs_scale_bilinear_f32_batch_dev(rgba_frame_f32 *const *targets, 
 }
 
 CVS_EXPORT void video_scale_bilinear_f32(rgba_frame_f32 *target, v2f tp, rgba_frame_f32 *source, v2f sp, v2f fac) {
-    if (cvs_enter() != 0) { box2i_set_empty(&target->current_window); return; }
-    hipStream_t s = cvs_pick_stream(NULL);
-    cvs_staged d_t = { 0 }, d_s = { 0 };
-    rgba_frame_f32 ft = *target, fs = *source;
-    int rc = cvs_stage_in(&d_t, target->data, cvs_box_pixels(&target->full_window) * sizeof(rgba_f32), 1, s);
-    if (rc == 0) rc = cvs_stage_in(&d_s, source->data, cvs_box_pixels(&source->full_window) * sizeof(rgba_f32), !box2i_is_empty(&source->current_window), s);
-    ft.data = d_t.dev; fs.data = d_s.dev;
-    if (rc == 0) rc = cvs_scale_bilinear_f32_dev(&ft, tp, &fs, sp, fac, s);
-    if (rc == 0) rc = cvs_stage_out(&d_t, target->data, s);
+    cvs_bridge br;
+    rgba_frame_f32 ft, fs;
+    cvs_bridge_open(&br);
+    CVS_BRIDGE_FRAME(&br, ft, target, CVS_BRIDGE_UPLOAD);
+    /* the scaler does not run in place: a source that is the target keeps a block of its own */
+    CVS_BRIDGE_FRAME(&br, fs, source, CVS_BRIDGE_PRIVATE | (box2i_is_empty(&source->current_window) ? 0 : CVS_BRIDGE_UPLOAD));
+    CVS_BRIDGE_CALL(&br, cvs_scale_bilinear_f32_dev, &ft, tp, &fs, sp, fac);
     target->current_window = ft.current_window;
-    if (rc != 0) box2i_set_empty(&target->current_window);
-    cvs_stage_free(&d_t); cvs_stage_free(&d_s);
+    if (cvs_bridge_close(&br, target->data) != 0) box2i_set_empty(&target->current_window);
 }
 
 CVS_EXPORT void video_scale_bilinear_f32_pull(rgba_frame_f32 *target, v2f tp, video_source *source, int frame,

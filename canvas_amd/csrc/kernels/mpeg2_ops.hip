@@ -14,25 +14,21 @@
 // (2cx, 2cx+1), eight luma bytes, Cb and Cr of both fields.  The column 2cx-1 comes from the left lane's encode
 // (__shfl_up); lane 0 of every wave computes the column pair left of the wave's first one for that purpose only, so a
 // wave produces 63 chroma columns per unit of work and every lane runs the same instructions.
-// The 128 KiB table: for rasters above a megapixel it is staged into LDS by one 1024-lane workgroup per CU (persistent,
-// strided over the units); up to a megapixel the lanes gather it from L2 through the vector L1 (256-lane workgroups, six per
-// CU), which spares the staging that a small raster does not earn back.  Measured: profiles/mpeg2, DESIGN.md 4.5.
+// The 128 KiB table: staged into LDS or gathered from L2, by the raster's size; the launch is persistent, strided over the units
+// (table_placement.hpp).
 // Algorithmic bytes: 8 read + 1.5 written per source pixel; measured and what bounds it: DESIGN.md 4.5.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "pixel_math.hpp"
+#include "table_placement.hpp"
 
 namespace {
 
-constexpr int kCols = 63, kTable = 65536;
-// where the table is read from: staged into LDS by 1024-lane workgroups, one per CU (the table fills the LDS), or gathered
-// from L2 / the vector L1 by 256-lane workgroups, several per CU.  The diagnostic build also has kTableLdsUnstaged: the LDS
-// form without the staging copy (timing only: its pixels are wrong), which isolates what the staging costs.
-enum { kTableLds = 0, kTableL2 = 1, kTableLdsUnstaged = 2 };
-// Chosen by measurement (profiles/mpeg2): staging costs every workgroup ~2 us before its first pixel, which a small raster does
-// not earn back -- 720x480: 4.4 us gathering vs 8.1 staged; 1920x1080: 12.9 vs 11.3; 3840x2160: 37.2 vs 22.3.  The switch
-// sits between the two measured sizes, at one megapixel.
-constexpr long long kGatherUpTo = 1LL << 20;
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
+constexpr int kCols = 63;
+// beside the two placements of table_placement.hpp the diagnostic build has the LDS form without the staging copy (timing only:
+// its pixels are wrong), which isolates what the staging costs
+enum { kTableLdsUnstaged = 2 };
 typedef uint32_t v4 __attribute__((ext_vector_type(4)));
 typedef uint32_t v4a8 __attribute__((ext_vector_type(4), aligned(8)));     // a pixel pair: 8-byte aligned only
 
@@ -111,9 +107,7 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_subsample(cvk_dv_planes pl, cvk
         fetch_block(frame, w, (u - k * chunks) * kCols + lane - 1, k, cw, px);
     }
     if (TABLE == kTableLds || (TABLE == kTableLdsUnstaged && units < 0)) {     // (the unstaged form: a copy that never runs)
-        const uint4 *src = reinterpret_cast<const uint4 *>(lut);
-        uint4 *dst = reinterpret_cast<uint4 *>(lds);
-        for (int i = threadIdx.x; i < kTable * 2 / 16; i += LANES) dst[i] = src[i];
+        cvs::stage_table<LANES>(lds, lut);
         __syncthreads();
     }
     for (; u < units; u += stride) {
@@ -157,9 +151,8 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_subsample(cvk_dv_planes pl, cvk
 template <int TABLE, int LANES>
 static void launch(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int width, long long chunks, long long units, const uint16_t *lut, long long most,
                    hipStream_t s) {
-    const long long want = (units + LANES / 64 - 1) / (LANES / 64);      // no workgroup without work of its own
-    hipLaunchKernelGGL((k_mpeg2_subsample<TABLE, LANES>), dim3((unsigned)(want < most ? want : most)), dim3(LANES), 0, s, *pl, frame, w, width,
-                       (int)chunks, (int)units, lut);
+    hipLaunchKernelGGL((k_mpeg2_subsample<TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, *pl, frame, w, width, (int)chunks,
+                       (int)units, lut);
 }
 
 }  // namespace
@@ -170,12 +163,12 @@ extern "C" int cvk_mpeg2_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_
     if (units > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
     const long long n = cus > 0 ? cus : 256;
     hipStream_t s = (hipStream_t)stream;
-    int table = (long long)width * (long long)height <= kGatherUpTo ? kTableL2 : kTableLds;
-    if (const char *e = CVS_DIAG_ENV("CVS_MPEG2_TABLE")) table = atoi(e);        // (diagnostic build only)
-    if (table == kTableL2) launch<kTableL2, 256>(pl, frame, w, width, chunks, units, lut, n * 6, s);
+    const int table = cvs::table_placement((long long)width * (long long)height);
+    const long long most = cvs::table_workgroups(table, n);
+    if (table == kTableL2) launch<kTableL2, cvs::kTableL2Lanes>(pl, frame, w, width, chunks, units, lut, most, s);
 #ifdef CVS_DIAG
-    else if (table == kTableLdsUnstaged) launch<kTableLdsUnstaged, 1024>(pl, frame, w, width, chunks, units, lut, n, s);
+    else if (table == kTableLdsUnstaged) launch<kTableLdsUnstaged, cvs::kTableLdsLanes>(pl, frame, w, width, chunks, units, lut, most, s);
 #endif
-    else launch<kTableLds, 1024>(pl, frame, w, width, chunks, units, lut, n, s);
+    else launch<kTableLds, cvs::kTableLdsLanes>(pl, frame, w, width, chunks, units, lut, most, s);
     return (int)hipGetLastError();
 }

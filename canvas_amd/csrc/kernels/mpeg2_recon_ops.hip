@@ -23,21 +23,18 @@
 // chroma rows per plane (interlaced: field row j+1 of each field; progressive: rows 2j+1, 2j+2); the rest stay in a register
 // ring, and the next group's bytes are loaded before the current group is worked out.  One 16-byte store per row and lane
 // where the pixel pair is aligned and inside the window, 8-byte stores otherwise.
-// The 128 KiB table: staged into LDS by one 1024-lane workgroup per CU above kGatherUpTo pixels, gathered from L2 through the
-// vector L1 by 256-lane workgroups below it (measured: profiles/mpeg2).
+// The 128 KiB table: staged into LDS or gathered from L2, by the raster's size (table_placement.hpp).
 // Algorithmic bytes: 1.5 read + 8 written per pixel.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "pixel_math.hpp"
+#include "table_placement.hpp"
 
 namespace {
 
-constexpr int kCols = 63, kTable = 65536, kMaxStrip = 16;
-enum { kTableLds = 0, kTableL2 = 1 };
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
+constexpr int kCols = 63, kMaxStrip = 16;
 enum { kInterlaced = 0, kProgressive = 1 };
-// Chosen by measurement (profiles/mpeg2/recon_*), kernel medians gathering vs staged: 720x480 4.9 vs 8.1 us,
-// 1920x1080 12.5 vs 9.5, 3840x2160 42.7 vs 22.4 (interlaced) -- the same crossover as k_mpeg2_subsample's.
-constexpr long long kGatherUpTo = 1LL << 20;
 // the chroma rows a group keeps: interlaced {field 0: j-1, j, j+1; field 1: j-1, j, j+1}, progressive {2j-1, 2j, 2j+1, 2j+2}
 template <int SITING> struct Ring { static constexpr int n = SITING == kInterlaced ? 6 : 4; };
 typedef uint32_t v4 __attribute__((ext_vector_type(4)));
@@ -129,11 +126,7 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_reconstruct(cvk_view frame, cvk
     __shared__ __attribute__((aligned(16))) uint16_t lds[kTable];
     __shared__ float dec_y[256], dec_c[256];
     const uint16_t *t = TABLE == kTableL2 ? lut : lds;
-    if (TABLE == kTableLds) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(lut);
-        uint4 *dst = reinterpret_cast<uint4 *>(lds);
-        for (int i = threadIdx.x; i < kTable * 2 / 16; i += LANES) dst[i] = src[i];
-    }
+    if (TABLE == kTableLds) cvs::stage_table<LANES>(lds, lut);      // (the wait is the __syncthreads() below)
     for (int i = threadIdx.x; i < 256; i += LANES) {
         dec_y[i] = ((float)i - 16.0f) / 219.0f;
         dec_c[i] = ((float)i - 128.0f) / 224.0f;
@@ -195,9 +188,8 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_reconstruct(cvk_view frame, cvk
 template <int SITING, int TABLE, int LANES>
 static void launch(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, const Mat &m, int width, int height, int ka, int ja, int jb, int strip,
                    long long chunks, long long units, const uint16_t *lut, long long most, hipStream_t s) {
-    const long long want = (units + LANES / 64 - 1) / (LANES / 64);      // no workgroup without work of its own
-    hipLaunchKernelGGL((k_mpeg2_reconstruct<SITING, TABLE, LANES>), dim3((unsigned)(want < most ? want : most)), dim3(LANES), 0, s, frame, w, *pl, m,
-                       width, height, ka, ja, jb, strip, (int)chunks, (int)units, lut);
+    hipLaunchKernelGGL((k_mpeg2_reconstruct<SITING, TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, frame, w, *pl, m, width,
+                       height, ka, ja, jb, strip, (int)chunks, (int)units, lut);
 }
 
 // The strip is the fewest row groups that leave no unit without a wave: one trip per wave, no second round for a few waves.  Some
@@ -206,12 +198,12 @@ static void launch(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, const Ma
 template <int SITING>
 static void dispatch(int table, cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, const Mat &m, int width, int height, int ka, int ja, int jb,
                      long long chunks, long long groups, const uint16_t *lut, long long cus, hipStream_t s) {
-    const long long lanes = table == kTableL2 ? 256 : 1024, most = table == kTableL2 ? cus * 6 : cus, waves = most * (lanes / 64);
+    const long long lanes = table == kTableL2 ? cvs::kTableL2Lanes : cvs::kTableLdsLanes, most = cvs::table_workgroups(table, cus), waves = most * (lanes / 64);
     long long strip = (chunks * groups + waves - 1) / waves;
     strip = strip < 1 ? 1 : (strip > kMaxStrip ? kMaxStrip : strip);
     const long long units = chunks * ((groups + strip - 1) / strip);
-    if (table == kTableL2) launch<SITING, kTableL2, 256>(frame, w, pl, m, width, height, ka, ja, jb, (int)strip, chunks, units, lut, most, s);
-    else launch<SITING, kTableLds, 1024>(frame, w, pl, m, width, height, ka, ja, jb, (int)strip, chunks, units, lut, most, s);
+    if (table == kTableL2) launch<SITING, kTableL2, cvs::kTableL2Lanes>(frame, w, pl, m, width, height, ka, ja, jb, (int)strip, chunks, units, lut, most, s);
+    else launch<SITING, kTableLds, cvs::kTableLdsLanes>(frame, w, pl, m, width, height, ka, ja, jb, (int)strip, chunks, units, lut, most, s);
 }
 
 }  // namespace
@@ -227,8 +219,8 @@ extern "C" int cvk_mpeg2_reconstruct(cvk_view frame, cvk_rect w, const cvk_dv_pl
     const Mat m = { mat[0], mat[1], mat[2], mat[3], mat[4], mat[5], mat[6], mat[7], mat[8] };
     const long long n = cus > 0 ? cus : 256;
     hipStream_t s = (hipStream_t)stream;
-    int table = (long long)width * (long long)height <= kGatherUpTo ? kTableL2 : kTableLds;
-    if (const char *e = CVS_DIAG_ENV("CVS_MPEG2_TABLE")) table = atoi(e) == kTableL2 ? kTableL2 : kTableLds;     // (diagnostic build only)
+    // (the diagnostic build's CVS_MPEG2_TABLE: any value other than the L2 form's means LDS here)
+    const int table = cvs::table_placement((long long)width * (long long)height) == kTableL2 ? kTableL2 : kTableLds;
     if (progressive) dispatch<kProgressive>(table, frame, w, pl, m, width, height, ka, ja, jb, chunks, groups, lut, n, s);
     else dispatch<kInterlaced>(table, frame, w, pl, m, width, height, ka, ja, jb, chunks, groups, lut, n, s);
     return (int)hipGetLastError();

@@ -10,9 +10,11 @@
  *                                   (no reference node: the inverse of the one above, for the 4:2:0 images decoders hand out)
  *
  * A coded image is a handful of byte planes in host memory (it is what a decoder hands over or an encoder
- * takes), so these nodes are where bytes cross PCIe: the reconstruction node uploads three planes
- * (518 400 bytes) and renders straight into the device frame it was given; the subsample node pulls its
- * source into a device frame, converts there and downloads the three planes.
+ * takes), so these nodes are where bytes cross PCIe: a reconstruction node uploads three planes
+ * (DV: 518 400 bytes) and renders straight into the device frame it was given; a subsample node pulls its
+ * source into a device frame, converts there and downloads the three planes.  On the device the planes of
+ * either kind live in one pooled block (planes_block below); the two reconstruction nodes share one render,
+ * the two subsample nodes one get_frame.
  */
 #include "pyext.h"
 
@@ -131,6 +133,76 @@ CVS_EXPORT PyTypeObject py_type_CodedImageSource = {
     .tp_flags = Py_TPFLAGS_DEFAULT | Py_TPFLAGS_BASETYPE, .tp_methods = cis_methods, .tp_getset = cis_getset,
 };
 
+/* ---------------------------------------------------------------- coded planes on the device */
+
+static size_t plane_bytes(const coded_image *image, int p) { return (size_t)image->stride[p] * (size_t)image->line_count[p]; }
+
+/* *dev = *host with its three planes in one pooled block, each on a 256-byte boundary; NULL when there is no memory */
+static char *planes_block(coded_image *dev, const coded_image *host, cvs_stream_t s) {
+    size_t off[3], total = 0;
+    for (int p = 0; p < 3; p++) { off[p] = total; total += (plane_bytes(host, p) + 255) & ~(size_t)255; }
+    char *block = cvs_pool_malloc(total ? total : 1, s);
+    *dev = *host;
+    for (int p = 0; p < 3; p++) dev->data[p] = block ? block + off[p] : NULL;
+    return block;
+}
+
+static int planes_copy(const coded_image *dev, const coded_image *host, bool up, cvs_stream_t s) {
+    int rc = 0;
+    for (int p = 0; rc == 0 && p < 3; p++)
+        rc = up ? cvs_memcpy_h2d(dev->data[p], host->data[p], plane_bytes(host, p), s) : cvs_memcpy_d2h(host->data[p], dev->data[p], plane_bytes(host, p), s);
+    return rc;
+}
+
+/* The render of both reconstruction nodes (native: f16): three planes up, the device entry straight into the device slot.
+ * `mpeg2`: the node's raster and flags, NULL for DV.  Planes missing or too small for the raster give an empty window (the
+ * entry refuses them before any read). */
+typedef struct { PyObject_HEAD CodedImageSourceHolder source; int width, height, flags; } py_mpeg2recon;
+
+static void planes_render(CodedImageSourceHolder *source, const py_mpeg2recon *mpeg2, int frame_index, rgba_frame_dev *f) {
+    box2i_set_empty(&f->current_window);
+    if (!source->source.obj || !source->source.funcs || !source->source.funcs->getFrame) return;
+    coded_image *image = source->source.funcs->getFrame(source->source.obj, frame_index, 0);
+    if (!image) return;
+    coded_image dev;
+    char *block = image->data[0] && image->data[1] && image->data[2] ? planes_block(&dev, image, f->stream) : NULL;
+    if (block) {
+        rgba_frame_f16 out = { f->data, f->full_window, f->full_window };
+        int rc = planes_copy(&dev, image, true, f->stream);
+        if (rc == 0) rc = mpeg2 ? cvs_reconstruct_mpeg2_dev(&out, &dev, mpeg2->width, mpeg2->height, mpeg2->flags, f->stream) : cvs_reconstruct_dv_dev(&out, &dev, f->stream);
+        if (rc == 0) f->current_window = out.current_window;
+        /* the host planes may be freed below: the uploads must have left them */
+        cvs_stream_sync(f->stream);
+        cvs_pool_free(block, f->stream);
+    }
+    if (image->free_func) image->free_func(image);
+}
+
+/* The get_frame of both subsample nodes: pull the raster's window into a device frame, subsample there, download the planes.
+ * DV: 720x480 at y = -1 (DVSubsampleFilter.c:55-56), chroma w/4 x h; MPEG-2: (0,0)-(w-1,h-1), chroma w/2 x h/2. */
+static coded_image *planes_from_source(video_source *source, int frame, int w, int h, bool dv) {
+    const int cw = dv ? w / 4 : w / 2, ch = dv ? h : h / 2, y0 = dv ? -1 : 0;
+    const int strides[3] = { w, cw, cw }, lines[3] = { h, ch, ch };
+    box2i window;
+    box2i_set(&window, 0, y0, w - 1, y0 + h - 1);
+    coded_image *out = coded_image_alloc(strides, lines, 3), dev;
+    if (!out) return NULL;
+    rgba_frame_dev d = { cvs_pool_malloc(frame_bytes(&window, CVS_FORMAT_F16), NULL), CVS_FORMAT_F16, window, window, NULL };
+    char *block = planes_block(&dev, out, NULL);
+    int rc = (d.data && block) ? 0 : -1;
+    if (rc == 0) {
+        video_get_frame_dev(source, frame, &d);
+        rgba_frame_f16 in = { d.data, d.full_window, d.current_window };
+        /* DV: the pulled frame is scratch, no need to leave it encoded */
+        rc = dv ? cvs_subsample_dv_dev(&dev, &in, 0, NULL) : cvs_subsample_mpeg2_dev(&dev, &in, w, h, NULL);
+        if (rc == 0) rc = planes_copy(&dev, out, false, NULL);
+    }
+    cvs_pool_free(block, NULL);
+    cvs_pool_free(d.data, NULL);
+    if (rc != 0) { out->free_func(out); return NULL; }
+    return out;
+}
+
 /* ---------------------------------------------------------------- DVReconstructionFilter */
 
 typedef struct { PyObject_HEAD CodedImageSourceHolder source; } py_dvrecon;
@@ -146,31 +218,7 @@ static void recon_dealloc(py_dvrecon *self) {
     Py_TYPE(self)->tp_free((PyObject *)self);
 }
 
-static void recon_render(PyObject *o, int frame_index, rgba_frame_dev *f) {      /* native: f16 */
-    py_dvrecon *self = (py_dvrecon *)o;
-    box2i_set_empty(&f->current_window);
-    if (!self->source.source.obj || !self->source.source.funcs || !self->source.source.funcs->getFrame) return;
-    coded_image *image = self->source.source.funcs->getFrame(self->source.source.obj, frame_index, 0);
-    if (!image) return;
-    /* three planes up, in one pooled block */
-    size_t off[3], total = 0;
-    bool ok = image->data[0] && image->data[1] && image->data[2];
-    for (int p = 0; ok && p < 3; p++) { off[p] = total; total += (((size_t)image->stride[p] * (size_t)image->line_count[p]) + 255) & ~(size_t)255; }
-    char *block = ok ? cvs_pool_malloc(total ? total : 1, f->stream) : NULL;
-    if (block) {
-        coded_image dev = *image;
-        for (int p = 0; ok && p < 3; p++) {
-            dev.data[p] = block + off[p];
-            ok = cvs_memcpy_h2d(dev.data[p], image->data[p], (size_t)image->stride[p] * (size_t)image->line_count[p], f->stream) == 0;
-        }
-        rgba_frame_f16 out = { f->data, f->full_window, f->full_window };
-        if (ok && cvs_reconstruct_dv_dev(&out, &dev, f->stream) == 0) f->current_window = out.current_window;
-        /* the host planes may be freed below: the uploads must have left them */
-        cvs_stream_sync(f->stream);
-        cvs_pool_free(block, f->stream);
-    }
-    if (image->free_func) image->free_func(image);
-}
+static void recon_render(PyObject *o, int frame_index, rgba_frame_dev *f) { planes_render(&((py_dvrecon *)o)->source, NULL, frame_index, f); }
 DEFINE_NODE_VTABLE(recon, CVS_FORMAT_F16, 1, 0)
 static void *recon_unused[] __attribute__((unused)) = { (void *)recon_slot_32 };
 static PyGetSetDef recon_getset[] = { { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &recon_capsule }, { NULL } };
@@ -196,31 +244,7 @@ static void sub_dealloc(py_dvsub *self) {
     Py_TYPE(self)->tp_free((PyObject *)self);
 }
 
-static coded_image *sub_get_frame(py_dvsub *self, int frame, int quality) {
-    const int strides[3] = { 720, 180, 180 }, lines[3] = { 480, 480, 480 };
-    box2i window;
-    box2i_set(&window, 0, -1, 719, 478);                   /* DVSubsampleFilter.c:55-56 */
-    coded_image *out = coded_image_alloc(strides, lines, 3);
-    if (!out) return NULL;
-    rgba_frame_dev d = { NULL, CVS_FORMAT_F16, window, window, NULL };
-    size_t off[3], total = 0;
-    for (int p = 0; p < 3; p++) { off[p] = total; total += (((size_t)strides[p] * 480) + 255) & ~(size_t)255; }
-    d.data = cvs_pool_malloc(frame_bytes(&window, CVS_FORMAT_F16), NULL);
-    char *block = cvs_pool_malloc(total, NULL);
-    int rc = (d.data && block) ? 0 : -1;
-    if (rc == 0) {
-        video_get_frame_dev(self->source, frame, &d);
-        coded_image dev = *out;
-        for (int p = 0; p < 3; p++) dev.data[p] = block + off[p];
-        rgba_frame_f16 in = { d.data, d.full_window, d.current_window };
-        rc = cvs_subsample_dv_dev(&dev, &in, 0, NULL);     /* the pulled frame is scratch: no need to leave it encoded */
-        for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_d2h(out->data[p], dev.data[p], (size_t)strides[p] * 480, NULL);
-    }
-    cvs_pool_free(block, NULL);
-    cvs_pool_free(d.data, NULL);
-    if (rc != 0) { out->free_func(out); return NULL; }
-    return out;
-}
+static coded_image *sub_get_frame(py_dvsub *self, int frame, int quality) { return planes_from_source(self->source, frame, 720, 480, true); }
 
 static coded_image_source_funcs sub_funcs = { 0, (coded_image_getFrameFunc)sub_get_frame };
 static PyGetSetDef sub_getset[] = { { CODED_IMAGE_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Coded image source C API.", &sub_capsule }, { NULL } };
@@ -234,8 +258,7 @@ static PyTypeObject py_type_DVSubsampleFilter = {
 /* ---------------------------------------------------------------- MPEG2SubsampleFilter */
 
 /* src/process/MPEG2SubsampleFilter.c (GL-only in the reference, video_subsample_mpeg2_gl): the same node on the device
- * entry, with the raster as a keyword (the reference's 720x480 by default).  Pull (0,0)-(W-1,H-1) into a device frame,
- * subsample there, download Y' W x H and Cb, Cr W/2 x H/2. */
+ * entry, with the raster as a keyword (the reference's 720x480 by default). */
 typedef struct { PyObject_HEAD video_source *source; int width, height; } py_mpeg2sub;
 
 static int mpeg2_init(py_mpeg2sub *self, PyObject *args, PyObject *kw) {
@@ -258,32 +281,7 @@ static void mpeg2_dealloc(py_mpeg2sub *self) {
     Py_TYPE(self)->tp_free((PyObject *)self);
 }
 
-static coded_image *mpeg2_get_frame(py_mpeg2sub *self, int frame, int quality) {
-    const int w = self->width, h = self->height;
-    const int strides[3] = { w, w / 2, w / 2 }, lines[3] = { h, h / 2, h / 2 };
-    box2i window;
-    box2i_set(&window, 0, 0, w - 1, h - 1);
-    coded_image *out = coded_image_alloc(strides, lines, 3);
-    if (!out) return NULL;
-    rgba_frame_dev d = { NULL, CVS_FORMAT_F16, window, window, NULL };
-    size_t off[3], total = 0;
-    for (int p = 0; p < 3; p++) { off[p] = total; total += (((size_t)strides[p] * (size_t)lines[p]) + 255) & ~(size_t)255; }
-    d.data = cvs_pool_malloc(frame_bytes(&window, CVS_FORMAT_F16), NULL);
-    char *block = cvs_pool_malloc(total, NULL);
-    int rc = (d.data && block) ? 0 : -1;
-    if (rc == 0) {
-        video_get_frame_dev(self->source, frame, &d);
-        coded_image dev = *out;
-        for (int p = 0; p < 3; p++) dev.data[p] = block + off[p];
-        rgba_frame_f16 in = { d.data, d.full_window, d.current_window };
-        rc = cvs_subsample_mpeg2_dev(&dev, &in, w, h, NULL);
-        for (int p = 0; rc == 0 && p < 3; p++) rc = cvs_memcpy_d2h(out->data[p], dev.data[p], (size_t)strides[p] * (size_t)lines[p], NULL);
-    }
-    cvs_pool_free(block, NULL);
-    cvs_pool_free(d.data, NULL);
-    if (rc != 0) { out->free_func(out); return NULL; }
-    return out;
-}
+static coded_image *mpeg2_get_frame(py_mpeg2sub *self, int frame, int quality) { return planes_from_source(self->source, frame, self->width, self->height, false); }
 
 static coded_image_source_funcs mpeg2_funcs = { 0, (coded_image_getFrameFunc)mpeg2_get_frame };
 static PyObject *mpeg2_capsule;
@@ -298,9 +296,7 @@ static PyTypeObject py_type_MPEG2SubsampleFilter = {
 /* ---------------------------------------------------------------- MPEG2ReconstructionFilter */
 
 /* coded planes -> half RGBA on the device entry (DESIGN.md "MPEG-2 4:2:0 reconstruction"): the raster, the siting and the matrix
- * as keywords.  Renders like DVReconstructionFilter: one pooled upload block for the three planes, straight into the device slot;
- * planes too small for the raster give an empty window (the entry refuses them before any read). */
-typedef struct { PyObject_HEAD CodedImageSourceHolder source; int width, height, flags; } py_mpeg2recon;
+ * as keywords.  Renders like DVReconstructionFilter (planes_render above, where py_mpeg2recon is declared). */
 
 static int mpeg2r_init(py_mpeg2recon *self, PyObject *args, PyObject *kw) {
     static char *kwlist[] = { "source", "size", "interlaced", "matrix", NULL };
@@ -335,34 +331,7 @@ static void mpeg2r_dealloc(py_mpeg2recon *self) {
     Py_TYPE(self)->tp_free((PyObject *)self);
 }
 
-static void mpeg2r_render(PyObject *o, int frame_index, rgba_frame_dev *f) {      /* native: f16 */
-    py_mpeg2recon *self = (py_mpeg2recon *)o;
-    box2i_set_empty(&f->current_window);
-    if (!self->source.source.obj || !self->source.source.funcs || !self->source.source.funcs->getFrame) return;
-    coded_image *image = self->source.source.funcs->getFrame(self->source.source.obj, frame_index, 0);
-    if (!image) return;
-    size_t off[3], bytes[3], total = 0;
-    bool ok = image->data[0] && image->data[1] && image->data[2];
-    for (int p = 0; ok && p < 3; p++) {
-        bytes[p] = (size_t)image->stride[p] * (size_t)image->line_count[p];
-        off[p] = total;
-        total += (bytes[p] + 255) & ~(size_t)255;
-    }
-    char *block = ok ? cvs_pool_malloc(total ? total : 1, f->stream) : NULL;
-    if (block) {
-        coded_image dev = *image;
-        for (int p = 0; ok && p < 3; p++) {
-            dev.data[p] = block + off[p];
-            ok = cvs_memcpy_h2d(dev.data[p], image->data[p], bytes[p], f->stream) == 0;
-        }
-        rgba_frame_f16 out = { f->data, f->full_window, f->full_window };
-        if (ok && cvs_reconstruct_mpeg2_dev(&out, &dev, self->width, self->height, self->flags, f->stream) == 0) f->current_window = out.current_window;
-        /* the host planes may be freed below: the uploads must have left them */
-        cvs_stream_sync(f->stream);
-        cvs_pool_free(block, f->stream);
-    }
-    if (image->free_func) image->free_func(image);
-}
+static void mpeg2r_render(PyObject *o, int frame_index, rgba_frame_dev *f) { planes_render(&((py_mpeg2recon *)o)->source, (py_mpeg2recon *)o, frame_index, f); }
 DEFINE_NODE_VTABLE(mpeg2r, CVS_FORMAT_F16, 1, 0)
 static void *mpeg2r_unused[] __attribute__((unused)) = { (void *)mpeg2r_slot_32 };
 static PyGetSetDef mpeg2r_getset[] = { { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &mpeg2r_capsule }, { NULL } };
