@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libcanvas_hip.so")
 CHAIN_MAX_LAYERS = 8
 DISPLAY_RGBA8, DISPLAY_ARGB32_PREMUL = 0, 1
 FIR_PATH_AUTO, FIR_PATH_PASSES, FIR_PATH_TILED, FIR_PATH_TABLES, FIR_PATH_HV, FIR_PATH_ONE_COLUMN, FIR_PATH_TWO_COLUMNS, FIR_PATH_STRIPS, FIR_PATH_TILES = 0, 1, 2, 4, 16, 32, 64, 128, 256
-FIR_KERNEL_NONE, FIR_KERNEL_WINDOW, FIR_KERNEL_HALVE, _FIR_KERNEL_RETIRED_3, FIR_KERNEL_VH, FIR_KERNEL_TILED, _FIR_KERNEL_RETIRED_6, FIR_KERNEL_TWO_PASS, FIR_KERNEL_PASS, FIR_KERNEL_HV, FIR_KERNEL_WINDOW_PAIR, FIR_KERNEL_HALVE_PAIR, FIR_KERNEL_TILE_VH = range(13)
+FIR_KERNEL_NONE, FIR_KERNEL_WINDOW, FIR_KERNEL_HALVE, _FIR_KERNEL_RETIRED_3, FIR_KERNEL_VH, FIR_KERNEL_TILED, _FIR_KERNEL_RETIRED_6, FIR_KERNEL_TWO_PASS, FIR_KERNEL_PASS, FIR_KERNEL_HV, FIR_KERNEL_WINDOW_PAIR, FIR_KERNEL_HALVE_PAIR, FIR_KERNEL_TILE_VH, FIR_KERNEL_UNSHARP = range(14)
 ARITH_SEPARATE, ARITH_CONTRACTED = 0, 1          # cvs_set_arithmetic: the reference's gcc build / its clang (contracting) build
 LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_TO_REC709, LUT_LINEAR_TO_SRGB = -1, 0, 1, 2, 3
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
@@ -176,6 +176,8 @@ SIGNATURES = {
     "cvs_frame_to_rgba8_intent_dev": (C.c_int, [_vp, _F16, C.c_int, C.c_float, _vp]),
     "video_frame_to_rgba8_intent": (C.c_int, [_vp, _F16, C.c_int, C.c_float]),
     "cvs_fir_blur_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, _vp]),
+    "cvs_unsharp_mask_f32_dev": (C.c_int, [_F32, _F32, _f32p, C.c_int, C.c_float, C.c_float, _vp]),
+    "cvs_unsharp_mask_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, C.c_float, C.c_float, _vp]),
     "cvs_blur_over_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, P(_F16), C.c_int, _vp]),
     "cvs_resample_lanczos_f32_dev": (C.c_int, [_F32, _F32, C.c_float, C.c_float, C.c_int, _vp]),
     "cvs_resample_lanczos_f16_dev": (C.c_int, [_F16, _F16, C.c_float, C.c_float, C.c_int, _vp]),

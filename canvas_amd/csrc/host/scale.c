@@ -643,6 +643,62 @@ CVS_EXPORT int cvs_fir_blur_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16
     return fir_blur(target, source, taps, ntaps, 1, stream, "cvs_fir_blur_f16_dev");
 }
 
+/* cvs_unsharp_mask_f32_dev / _f16_dev (DESIGN.md "Unsharp mask"): the blur entries' windows and refusals; per colour channel
+ * d = s - B, out = |d| < threshold ? s : s + amount * d with B the blur above, alpha the source's.  One sweep (unsharp_ops.hip)
+ * for the tap lists it has instances for; every other list: the blur above into a pooled f32 frame over the window, then the
+ * mask alone -- same f32 values through the same expression, the same codes. */
+static int unsharp_mask(void *target, const void *source, const float *taps, int ntaps, float amount, float threshold, int half,
+                        cvs_stream_t stream, const char *what) {
+    frame_ref t, src;
+    if (entry_refused(target, source, half, what, &t, &src)) return -1;
+    if (ntaps < 1 || !taps) { cvs_set_error("unsharp mask: need at least one tap"); box2i_set_empty(t.cur); return -1; }
+    hipStream_t s = cvs_pick_stream(stream);
+    box2i win;
+    box2i_intersect(&win, src.cur, t.full);
+    *t.cur = win;
+    /* the tap list picks the path; a window without pixels is taken by that path too (nothing to launch) */
+    const bool fused = blur_has_fast_kernel(taps, ntaps) && CVK(cvk_unsharp_supported)(ntaps);
+    t_fir_kernel = fused ? CVS_FIR_KERNEL_UNSHARP : CVS_FIR_KERNEL_NONE;
+    if (box2i_is_empty(&win)) return 0;
+    const any_frame tf = any_of(&t, half), sf = any_of(&src, half);
+    int rc;
+    if (fused) {
+        cvk_unsharp_params up;
+        memset(&up, 0, sizeof up);
+        up.target = cvs_view(tf.data, &tf.full);
+        up.source = cvs_view(sf.data, &sf.full);
+        up.half = half;
+        up.tx0 = win.min.x; up.ty0 = win.min.y; up.tx1 = win.max.x; up.ty1 = win.max.y;
+        up.sx0 = sf.cur.min.x; up.sy0 = sf.cur.min.y; up.sx1 = sf.cur.max.x; up.sy1 = sf.cur.max.y;
+        up.ntaps = ntaps;
+        up.amount = amount; up.threshold = threshold;
+        memcpy(up.taps, taps, sizeof(float) * (size_t)ntaps);
+        rc = CVK(cvk_unsharp)(&up, cvs_cus(), s);
+        if (rc != 0) { cvs_set_error("unsharp mask launch failed: %s", hipGetErrorString((hipError_t)rc)); rc = -1; }
+    } else {
+        any_frame mid = { NULL, win, win, 0 };
+        mid.data = cvs_pool_malloc(cvs_box_pixels(&win) * sizeof(rgba_f32), s);
+        if (!mid.data) { box2i_set_empty(t.cur); return -1; }
+        rc = blur_fused(&mid, &sf, &win, taps, ntaps, NULL, 0, NULL, s);
+        if (rc == 0) {
+            const cvk_rect r = { win.min.x, win.min.y, win.max.x, win.max.y };
+            rc = CVK(cvk_unsharp_combine)(cvs_view(tf.data, &tf.full), cvs_view(sf.data, &sf.full), cvs_view(mid.data, &mid.full), r, half, amount, threshold, s);
+            if (rc != 0) { cvs_set_error("unsharp mask launch failed: %s", hipGetErrorString((hipError_t)rc)); rc = -1; }
+        }
+        cvs_pool_free(mid.data, s);
+    }
+    if (rc != 0) box2i_set_empty(t.cur);
+    return rc;
+}
+
+CVS_EXPORT int cvs_unsharp_mask_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const float *taps, int ntaps, float amount, float threshold, cvs_stream_t s) {
+    return unsharp_mask(target, source, taps, ntaps, amount, threshold, 0, s, "cvs_unsharp_mask_f32_dev");
+}
+
+CVS_EXPORT int cvs_unsharp_mask_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const float *taps, int ntaps, float amount, float threshold, cvs_stream_t s) {
+    return unsharp_mask(target, source, taps, ntaps, amount, threshold, 1, s, "cvs_unsharp_mask_f16_dev");
+}
+
 /* A workspace whose lowest item is a blur node on an f16 source and whose higher items are f16 frames, pulled as
  * f16: workspace.c:530-544 fetches the base as f32 (the blur's own format, no rounding), blends every higher
  * item over it with video_mix_over_f32 at mix 1.0, and main.c:43-71 truncates the result.  One launch when every

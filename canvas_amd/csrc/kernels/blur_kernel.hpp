@@ -20,6 +20,9 @@
 // Algorithmic bytes: source pixel size + target pixel size per target pixel.  Bound: HBM up to about 5 taps; from 9 taps on
 // the issue of 2 passes x 2 channel pairs x NT x (multiply + add) -- separately rounded, as the reference build rounds
 // them, so no FMA -- takes longer than the memory traffic (4K, 9 taps: 0.045 ms against 0.024 ms of traffic).
+//
+// unsharp_ops.hip holds a second copy of this sweep (k_unsharp: STEP 1, no epilogue, no batch, plus the mask): a change to the
+// pipelining or to the order of the sums here has to be made there as well.
 #pragma once
 #include <cstdlib>
 #include <atomic>

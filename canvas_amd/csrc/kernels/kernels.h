@@ -50,6 +50,9 @@
 #define cvk_blur_halve_supported     cvk_blur_halve_supported_fma
 #define cvk_blur_halve_takes_pairs   cvk_blur_halve_takes_pairs_fma
 #define cvk_blur_halve               cvk_blur_halve_fma
+#define cvk_unsharp_supported        cvk_unsharp_supported_fma
+#define cvk_unsharp                  cvk_unsharp_fma
+#define cvk_unsharp_combine          cvk_unsharp_combine_fma
 #define cvk_dv_reconstruct           cvk_dv_reconstruct_fma
 #define cvk_dv_subsample             cvk_dv_subsample_fma
 #endif
@@ -267,6 +270,24 @@ int cvk_blur_halve_pair(const cvk_blur_halve_params *bp, int cus, void *stream);
 int cvk_blur_halve_takes_pairs(const cvk_blur_halve_params *bp);
 int cvk_blur_halve(const cvk_blur_halve_params *bp, int cus, void *stream);
 
+/* Unsharp mask (unsharp_ops.hip, DESIGN.md "Unsharp mask"): per colour channel d = s - B, out = |d| < threshold ? s : s + amount * d
+ * with B the blur of cvk_blur for the same taps and windows, alpha = the source's; source and target of one format.  cvk_unsharp:
+ * blur and mask in one sweep, 3..13 taps odd, all finite (cvk_unsharp_supported).  cvk_unsharp_combine: the mask alone over `r`,
+ * from a blur that exists as an f32 frame (`blurred`, any tap list). */
+typedef struct {
+    cvk_view target, source;
+    int half;                  /* 0: rgba_f32 pixels in and out, 1: rgba_f16 (widened on load, truncated on store) */
+    int tx0, ty0, tx1, ty1;    /* target rectangle */
+    int sx0, sy0, sx1, sy1;    /* the source's current window (contains the target rectangle) */
+    int ntaps;
+    int rows_per_wg;           /* 0: let the launcher choose */
+    float amount, threshold;
+    float taps[16];
+} cvk_unsharp_params;
+int cvk_unsharp_supported(int ntaps);
+int cvk_unsharp(const cvk_unsharp_params *up, int cus, void *stream);
+int cvk_unsharp_combine(cvk_view out, cvk_view src, cvk_view blurred, cvk_rect r, int half, float amount, float threshold, void *stream);
+
 /* display / export edge: f16 RGBA -> 4 bytes per pixel through a 65536-entry half->u8 table (device pointer,
  * 16-byte aligned); dst is packed over the rectangle */
 enum { CVK_DISPLAY_RGBA8 = 0, CVK_DISPLAY_ARGB32_PREMUL = 1 };
@@ -327,6 +348,9 @@ int cvk_blur_halve_pair_fma(const cvk_blur_halve_params *bp, int cus, void *stre
 int cvk_blur_halve_supported_fma(int ntaps1, int ntaps2);
 int cvk_blur_halve_takes_pairs_fma(const cvk_blur_halve_params *bp);
 int cvk_blur_halve_fma(const cvk_blur_halve_params *bp, int cus, void *stream);
+int cvk_unsharp_supported_fma(int ntaps);
+int cvk_unsharp_fma(const cvk_unsharp_params *up, int cus, void *stream);
+int cvk_unsharp_combine_fma(cvk_view out, cvk_view src, cvk_view blurred, cvk_rect r, int half, float amount, float threshold, void *stream);
 int cvk_dv_reconstruct_fma(cvk_view frame, cvk_rect cur, const cvk_dv_planes *pl, const cvk_dv_taps *tri, const uint16_t *lut, void *stream);
 int cvk_dv_subsample_fma(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, const cvk_dv_taps *tri, const uint16_t *lut, int encode_in_place, void *stream);
 #endif

@@ -61,6 +61,9 @@ PyObject *node1_set_source(node1 *self, PyObject *args);
 int node1_set_source_attr(node1 *self, PyObject *value, void *closure);
 extern PyMethodDef node1_methods[];
 
+/* a source that fills the f16 host slot only is half-native: its f32 pull is "pull f16, widen" (main.c:105-144) */
+static inline bool half_native(const video_source *src) { return src && src->funcs && src->funcs->get_frame && !src->funcs->get_frame_32; }
+
 /* frame objects (pyframes.c) */
 PyObject *py_RgbaFrameF16_new(box2i *full_window, rgba_frame_f16 **frame);
 PyObject *py_RgbaFrameF32_new(box2i *full_window, rgba_frame_f32 **frame);
@@ -75,6 +78,7 @@ int init_animation(PyObject *module);
 int init_dv(PyObject *module);
 int init_sources(PyObject *module);
 int init_fields(PyObject *module);
+int init_blur(PyObject *module);
 int init_workspace(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */

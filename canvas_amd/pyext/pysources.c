@@ -210,9 +210,6 @@ static void mix_render(PyObject *o, int frame_index, rgba_frame_dev *f) {       
     f->current_window = fa.current_window;
     cvs_pool_free(tb.data, f->stream);
 }
-/* a source that fills the f16 host slot only is half-native: its f32 pull is "pull f16, widen" (main.c:105-144) */
-static bool half_native(const video_source *src) { return src && src->funcs && src->funcs->get_frame && !src->funcs->get_frame_32; }
-
 /* f16 wanted and both inputs half-native: pull them as f16 and crossfade in one launch (widen, cross, truncate in
  * registers) instead of rendering f32 and narrowing; same arithmetic, a fifth of the traffic */
 static bool mix_render_half(py_mix *self, int frame_index, rgba_frame_dev *f) {

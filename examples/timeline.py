@@ -52,6 +52,7 @@ sequence.append((process.VideoPassThroughFilter(b, offset=20), 0, 20))
 pip_source = process.VideoGainOffsetFilter(process.SolidColorVideoSource((0.95, 0.95, 0.2, 0.6), box2i(0, 0, W - 1, H - 1)), gain=1.0)
 pip = process.VideoScaler(pip_source, target_point=(W - 360, 40), source_point=(0, 0), scale_factors=(0.25, 0.25),
                           source_rect=box2i(0, 0, W - 1, H - 1))
+pip = process.VideoUnsharpMaskFilter(pip, process.gaussian_taps(1.0, 5), amount=0.8, threshold=1.0 / 256)    # sharpen what the downscale softened
 title = process.SolidColorVideoSource((0.0, 0.0, 0.0, 0.7), box2i(0, H - 90, W - 1, H - 1))
 
 timeline = process.VideoWorkspace()

@@ -460,6 +460,17 @@ CVS_EXPORT int video_frame_to_rgba8_intent(void *dst_host, const rgba_frame_f16 
 
 /* blur node between two f16 frames (widen on load, f32 passes, truncate on store), one launch */
 CVS_EXPORT int cvs_fir_blur_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const float *taps, int ntaps, cvs_stream_t stream);
+/* Unsharp mask (DESIGN.md "Unsharp mask").  B = the blur of `source` exactly as cvs_fir_blur_*_dev computes it (same window:
+ * source.current_window clipped to target.full_window; same sums, in the arithmetic flavour in force).  Then per pixel of that
+ * window, in f32, every operation rounded on its own in both flavours:
+ *     for c in r, g, b:  d = s.c - B.c;  out.c = fabsf(d) < threshold ? s.c : s.c + amount * d;      out.a = s.a
+ * (a NaN d takes the sharpening branch; amount 0 returns the source's colours; threshold <= 0 sharpens everywhere).  f16 targets
+ * are truncated at the store, once.  Windows, refusals and return values as the blur entries'.  Odd lists of 3..13 finite taps
+ * run as ONE launch without an intermediate frame (cvs_fir_last_kernel() == CVS_FIR_KERNEL_UNSHARP -- the tap list decides,
+ * so also for a call whose window holds no pixel and that launches nothing); every other list as the
+ * blur into a pooled f32 frame followed by the mask, with the same result wherever both can run.  Not in place. */
+CVS_EXPORT int cvs_unsharp_mask_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const float *taps, int ntaps, float amount, float threshold, cvs_stream_t s);
+CVS_EXPORT int cvs_unsharp_mask_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const float *taps, int ntaps, float amount, float threshold, cvs_stream_t s);
 /* f16 pull of a workspace whose lowest item is a blur node on `source` and whose higher items are `overlays`
  * (bottom first); the blur result stays f32 until the final truncation, as workspace.c:530-544 would have it */
 CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *source, const float *taps, int ntaps,
@@ -506,7 +517,8 @@ enum { CVS_FIR_KERNEL_NONE = 0,
        CVS_FIR_KERNEL_HV = 9,          /* k_fir_hv: per-line tables, horizontal pass first, gather per target line */
        CVS_FIR_KERNEL_WINDOW_PAIR = 10,    /* k_blur_pair: the register-window blur with two columns per lane (f16, up to 13 taps) */
        CVS_FIR_KERNEL_HALVE_PAIR = 11,     /* k_blur_halve_pair: blur + Lanczos halving with two source columns per lane (f16) */
-       CVS_FIR_KERNEL_TILE_VH = 12 };      /* k_fir_tile_vh: the triangle scaler, vertical pass first, a workgroup per 128 x 16 tile (enlarging) */
+       CVS_FIR_KERNEL_TILE_VH = 12,        /* k_fir_tile_vh: the triangle scaler, vertical pass first, a workgroup per 128 x 16 tile (enlarging) */
+       CVS_FIR_KERNEL_UNSHARP = 13 };      /* k_unsharp: register-window blur and unsharp mask in one sweep (the mask's other path reports the blur kernel it used) */
 CVS_EXPORT int cvs_fir_last_kernel(void);
 /* How many FIR launches of the calling thread were chosen for a fused kernel that then did not launch and went to the next
  * kernel in line (same pixels, slower): each is also reported to the log handler as a warning.  A successful call leaves
