@@ -18,6 +18,7 @@ FIR_PATH_AUTO, FIR_PATH_PASSES, FIR_PATH_TILED, FIR_PATH_TABLES, FIR_PATH_HV, FI
 FIR_KERNEL_NONE, FIR_KERNEL_WINDOW, FIR_KERNEL_HALVE, _FIR_KERNEL_RETIRED_3, FIR_KERNEL_VH, FIR_KERNEL_TILED, _FIR_KERNEL_RETIRED_6, FIR_KERNEL_TWO_PASS, FIR_KERNEL_PASS, FIR_KERNEL_HV, FIR_KERNEL_WINDOW_PAIR, FIR_KERNEL_HALVE_PAIR, FIR_KERNEL_TILE_VH, FIR_KERNEL_UNSHARP = range(14)
 ARITH_SEPARATE, ARITH_CONTRACTED = 0, 1          # cvs_set_arithmetic: the reference's gcc build / its clang (contracting) build
 LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_TO_REC709, LUT_LINEAR_TO_SRGB = -1, 0, 1, 2, 3
+KEY_SHOW_MATTE = 1                                  # cvs_chroma_key.flags
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
@@ -33,6 +34,11 @@ class rgba_frame_dev(C.Structure):
 class chain_job(C.Structure):
     _fields_ = [("out", C.POINTER(rgba_frame_f16)), ("layers", C.POINTER(rgba_frame_f16) * CHAIN_MAX_LAYERS),
                 ("nlayers", C.c_int)]
+
+
+class chroma_key(C.Structure):
+    _fields_ = [("key", C.c_float * 3), ("tolerance", C.c_float), ("softness", C.c_float), ("spill", C.c_float),
+                ("spill_range", C.c_float), ("flags", C.c_int)]
 
 
 class coded_image(C.Structure):
@@ -178,6 +184,8 @@ SIGNATURES = {
     "cvs_fir_blur_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, _vp]),
     "cvs_unsharp_mask_f32_dev": (C.c_int, [_F32, _F32, _f32p, C.c_int, C.c_float, C.c_float, _vp]),
     "cvs_unsharp_mask_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, C.c_float, C.c_float, _vp]),
+    "cvs_chroma_key_f32_dev": (C.c_int, [_F32, _F32, P(chroma_key), _vp]),
+    "cvs_chroma_key_f16_dev": (C.c_int, [_F16, _F16, P(chroma_key), _vp]),
     "cvs_blur_over_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, P(_F16), C.c_int, _vp]),
     "cvs_resample_lanczos_f32_dev": (C.c_int, [_F32, _F32, C.c_float, C.c_float, C.c_int, _vp]),
     "cvs_resample_lanczos_f16_dev": (C.c_int, [_F16, _F16, C.c_float, C.c_float, C.c_int, _vp]),

@@ -28,30 +28,11 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "pixel_math.hpp"
+#include "stream_common.hpp"
 
 namespace {
 
-constexpr int kLanes = 64, kMinSeg = 8, kMaxSeg = 64, kWavesPerCu = 16;
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t v2 __attribute__((ext_vector_type(2)));
-
-// PIX pixels of one row as dwords (lo = g:r, hi = a:b per pixel); the second pixel's dwords stay zero when PIX == 1
-template <int PIX>
-__device__ __forceinline__ v4 load_px(const cvk_view &v, int x, int y) {
-    const char *p = static_cast<const char *>(v.data) + ((long long)(y - v.fy0) * v.pitch + (x - v.fx0)) * 8;
-    if (PIX == 2) return *reinterpret_cast<const v4 *>(p);
-    const v2 t = *reinterpret_cast<const v2 *>(p);
-    return v4{ t.x, t.y, 0u, 0u };
-}
-
-// m0 / m1: the first / second pixel lies inside the window
-template <int PIX>
-__device__ __forceinline__ void store_px(const cvk_view &v, int x, int y, v4 c, bool m0, bool m1) {
-    char *p = static_cast<char *>(v.data) + ((long long)(y - v.fy0) * v.pitch + (x - v.fx0)) * 8;
-    if (PIX == 2 && m0 && m1) { __builtin_nontemporal_store(c, reinterpret_cast<v4 *>(p)); return; }
-    if (m0) __builtin_nontemporal_store(v2{ c.x, c.y }, reinterpret_cast<v2 *>(p));
-    if (PIX == 2 && m1) __builtin_nontemporal_store(v2{ c.z, c.w }, reinterpret_cast<v2 *>(p) + 1);
-}
+using namespace rowstream;
 
 // two channels: upper * 0.5 + lower * 0.5, one rounding in the sum
 __device__ __forceinline__ uint32_t mean2(uint32_t upper, uint32_t lower) {
@@ -84,19 +65,11 @@ __device__ __forceinline__ v4 soft_px(v4 a, v4 b, v4 c) {
     return r;
 }
 
-// what every kernel starts with: the lane's columns and the segment's rows.  `w` is the window written, `xs` the column of lane
-// 0 of the first workgroup (w.x0, or the pair boundary left of it), `seg` the rows per segment.
-#define FIELD_LANE(w, xs, seg)                                                                      \
-    const int x = (xs) + PIX * (int)(blockIdx.x * kLanes + threadIdx.x);                            \
-    const bool m0 = x >= (w).x0 && x <= (w).x1, m1 = PIX == 2 && x + 1 >= (w).x0 && x + 1 <= (w).x1; \
-    if (!m0 && !m1) return;                                                                         \
-    const int y0 = (w).y0 + (int)blockIdx.y * (seg), y1 = min(y0 + (seg) - 1, (w).y1);
-
 // `rows`: the rows of in's current window (w's columns lie inside it).  The walk goes over the rows r of the kept field from the
 // one at or above y0 to the one at or below y1 + 1: row r - 1 is made from rows r - 2 and r, row r is copied.
 template <int PIX>
 __global__ __launch_bounds__(kLanes) void k_field_to_frame(cvk_view out, cvk_view in, cvk_rect w, int rows0, int rows1, int field, int xs, int seg) {
-    FIELD_LANE(w, xs, seg)
+    ROWSTREAM_LANE(w, xs, seg)
     const int first = (y0 & 1) == field ? y0 : y0 - 1;
     const v4 zero = { 0u, 0u, 0u, 0u };
     bool have_prev = false, have_cur = first >= rows0 && first <= rows1;
@@ -113,7 +86,7 @@ __global__ __launch_bounds__(kLanes) void k_field_to_frame(cvk_view out, cvk_vie
 
 template <int PIX>
 __global__ __launch_bounds__(kLanes) void k_soften_fields(cvk_view out, cvk_view in, cvk_rect w, int rows0, int rows1, int xs, int seg) {
-    FIELD_LANE(w, xs, seg)
+    ROWSTREAM_LANE(w, xs, seg)
     v4 cur = load_px<PIX>(in, x, y0);
     v4 prev = y0 - 1 >= rows0 ? load_px<PIX>(in, x, y0 - 1) : cur;
     bool have_next = y0 + 1 <= rows1;
@@ -131,7 +104,7 @@ __global__ __launch_bounds__(kLanes) void k_soften_fields(cvk_view out, cvk_view
 // ew / ow: the current windows of `even` and `odd`
 template <int PIX>
 __global__ __launch_bounds__(kLanes) void k_interlace_fields(cvk_view out, cvk_view even, cvk_view odd, cvk_rect w, cvk_rect ew, cvk_rect ow, int xs, int seg) {
-    FIELD_LANE(w, xs, seg)
+    ROWSTREAM_LANE(w, xs, seg)
     const bool e0 = x >= ew.x0 && x <= ew.x1, e1 = PIX == 2 && x + 1 >= ew.x0 && x + 1 <= ew.x1;
     const bool o0 = x >= ow.x0 && x <= ow.x1, o1 = PIX == 2 && x + 1 >= ow.x0 && x + 1 <= ow.x1;
 #pragma unroll 4
@@ -150,33 +123,6 @@ __global__ __launch_bounds__(kLanes) void k_interlace_fields(cvk_view out, cvk_v
         store_px<PIX>(out, x, y, c, m0, m1);
     }
 }
-
-// Two pixels per lane need every view to put the pairs (xs + 2k, xs + 2k + 1) on 16-byte boundaries in every row: base aligned,
-// even pitch, xs - fx0 even.  xs is the pair boundary of `out` at or left of the window; the inputs must share its parity.
-inline bool pair_view(const cvk_view &v, int xs) {
-    return (reinterpret_cast<uintptr_t>(v.data) & 15u) == 0 && (v.pitch & 1) == 0 && (((long long)xs - v.fx0) & 1) == 0;
-}
-
-struct Shape { int pix, xs, seg; dim3 grid; };
-
-// segments: enough one-wave workgroups for kWavesPerCu waves on every CU where the window has the rows for it, never shorter than
-// kMinSeg rows (the seam rows are read twice)
-inline Shape shape(const cvk_rect &w, bool pairs, int out_fx0, int cus) {
-    Shape s;
-    s.pix = pairs ? 2 : 1;
-    s.xs = pairs ? w.x0 - (int)(((long long)w.x0 - out_fx0) & 1) : w.x0;
-    const long long cols = (long long)w.x1 - s.xs + 1, rows = (long long)w.y1 - w.y0 + 1;
-    const long long chunks = (cols + s.pix * kLanes - 1) / (s.pix * kLanes);
-    const long long waves = (long long)(cus > 0 ? cus : 256) * kWavesPerCu;
-    long long seg = (rows * chunks + waves - 1) / waves;
-    seg = seg < kMinSeg ? kMinSeg : (seg > kMaxSeg ? kMaxSeg : seg);
-    if ((rows + seg - 1) / seg > 65535) seg = (rows + 65534) / 65535;
-    s.seg = (int)seg;
-    s.grid = dim3((unsigned)chunks, (unsigned)((rows + seg - 1) / seg), 1);
-    return s;
-}
-
-inline bool rect_empty(const cvk_rect &r) { return r.x1 < r.x0 || r.y1 < r.y0; }
 
 }  // namespace
 

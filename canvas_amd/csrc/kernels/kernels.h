@@ -321,6 +321,17 @@ int cvk_field_to_frame(cvk_view out, cvk_view in, cvk_rect w, cvk_rect in_cur, i
 int cvk_soften_fields(cvk_view out, cvk_view in, cvk_rect w, cvk_rect in_cur, int cus, void *stream);
 int cvk_interlace_fields(cvk_view out, cvk_view even, cvk_view odd, cvk_rect w, cvk_rect even_cur, cvk_rect odd_cur, int cus, void *stream);
 
+/* Chroma key (key_ops.hip, DESIGN.md "Chroma key"): `w` inside both views, which are of one format (half: rgba_f16, else
+ * rgba_f32) and may be the same buffer.  What host/key.c worked out of a cvs_chroma_key: the key colour's Pb and Pr, the two
+ * reciprocals (read only where soft / fade say their width is > 0), spill clamped to [0, 1].  One arithmetic flavour: every
+ * operation is rounded on its own in both (the unit is not rebuilt with -DCVS_CONTRACT). */
+typedef struct {
+    float kpb, kpr, tolerance, inv_soft, inv_spill, spill;
+    int soft, fade;            /* softness > 0, spill_range > 0 */
+    int matte;                 /* (a', a', a', 1) instead of the keyed pixel */
+} cvk_key_params;
+int cvk_chroma_key(const cvk_key_params *kp, cvk_view out, cvk_view in, cvk_rect w, int half, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

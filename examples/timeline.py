@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A small timeline built from the same `fluggo.media.process` objects the Canvas editor creates
 (fluggo/editor/graph/video.py): two clips cut together with a crossfade, a picture-in-picture layer scaled down over
-them, a title bar on top.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
+them, a chroma-keyed layer, a title bar on top.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
 
     python examples/timeline.py [out_dir]        # writes frame_000.png ... (and prints Mpx/s)
 """
@@ -53,12 +53,16 @@ pip_source = process.VideoGainOffsetFilter(process.SolidColorVideoSource((0.95, 
 pip = process.VideoScaler(pip_source, target_point=(W - 360, 40), source_point=(0, 0), scale_factors=(0.25, 0.25),
                           source_rect=box2i(0, 0, W - 1, H - 1))
 pip = process.VideoUnsharpMaskFilter(pip, process.gaussian_taps(1.0, 5), amount=0.8, threshold=1.0 / 256)    # sharpen what the downscale softened
+# a keyed layer: a 'green-screen shot' (a green ground whose colour drifts towards the subject's orange) loses its ground and its spill
+shot = process.SolidColorVideoSource(process.LerpFunc((0.08, 0.62, 0.12, 1.0), (0.8, 0.45, 0.1, 1.0), FRAMES), box2i(60, 60, 420, 300))
+keyed = process.VideoChromaKeyFilter(shot, key=(0.08, 0.62, 0.12, 1.0), tolerance=0.08, softness=0.25, spill=0.8, spill_range=0.4)
 title = process.SolidColorVideoSource((0.0, 0.0, 0.0, 0.7), box2i(0, H - 90, W - 1, H - 1))
 
 timeline = process.VideoWorkspace()
 timeline.add(source=sequence, x=0, length=FRAMES, z=0, offset=0)
 timeline.add(source=pip, x=10, length=40, z=1, offset=0)
-timeline.add(source=title, x=0, length=FRAMES, z=2, offset=0)
+timeline.add(source=keyed, x=0, length=FRAMES, z=2, offset=0)
+timeline.add(source=title, x=0, length=FRAMES, z=3, offset=0)
 
 window = box2i(0, 0, W - 1, H - 1)
 timeline.get_frame_rgba8(0, window)                       # first use: tables, code objects

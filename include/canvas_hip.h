@@ -471,6 +471,35 @@ CVS_EXPORT int cvs_fir_blur_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16
  * blur into a pooled f32 frame followed by the mask, with the same result wherever both can run.  Not in place. */
 CVS_EXPORT int cvs_unsharp_mask_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const float *taps, int ntaps, float amount, float threshold, cvs_stream_t s);
 CVS_EXPORT int cvs_unsharp_mask_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const float *taps, int ntaps, float amount, float threshold, cvs_stream_t s);
+/* Chroma key (DESIGN.md "Chroma key"): alpha from a picture's distance to a key colour in the Pb, Pr plane, with spill
+ * suppression.  Frames are un-premultiplied, so the key scales alpha and leaves colour alone but for the despill; the over
+ * entries then composite the result as it is.  win = source.current_window ∩ target.full_window; on success
+ * target.current_window = win (0 is returned for an empty one too), pixels of `target` outside it keep what they held.  -1 with
+ * a message and an empty target window for a NULL pointer, a source window outside its full window, a non-finite key[], a
+ * non-finite or negative tolerance, softness or spill_range, and a failed launch.  `target` may be the source frame itself.
+ * Per pixel s of win, in f32 (a half widened exactly), every operation rounded on its own in both arithmetic flavours, with
+ * the Rec.709 R'G'B' -> Y'PbPr rows c0 = 0.2126f, 0.7152f, 0.0722f; c1 = -0.114572f, -0.385428f, 0.5f; c2 = 0.5f, -0.454153f,
+ * -0.045847f and kpb, kpr the key colour's pb, pr by the same expressions:
+ *     pb = (s.r*c10 + s.g*c11) + s.b*c12 ;  pr = (s.r*c20 + s.g*c21) + s.b*c22
+ *     dx = pb - kpb ; dy = pr - kpr ; d = sqrtf(dx*dx + dy*dy)                  (correctly rounded)
+ *     ramp(t) = (t < 1) ? ((t > 0) ? t : 0) : 1                                   (NaN -> 1: such a pixel is kept)
+ *     m = softness > 0 ? ramp((d - tolerance) * (1.0f / softness)) : (d <= tolerance ? 0 : 1) ;   a' = s.a * m
+ *     spill > 0:  q = spill_range > 0 ? ramp((d - tolerance) * (1.0f / spill_range)) : (d <= tolerance ? 0 : 1)
+ *                 ws = spill * (1 - q) ;  y = (s.r*c00 + s.g*c01) + s.b*c02 ;  for c in r, g, b:  e = y - s.c ; f = ws * e ; c' = s.c + f
+ *     else        c' = s.c, code for code
+ *     out = (flags & CVS_KEY_SHOW_MATTE) ? (a', a', a', 1) : (r', g', b', a')
+ * f16 targets are truncated once, at the store. */
+enum { CVS_KEY_SHOW_MATTE = 1 };
+typedef struct cvs_chroma_key {
+    float key[3];       /* the colour to remove, in the frame's own RGB */
+    float tolerance;    /* chroma distance up to which a pixel is removed entirely */
+    float softness;     /* width of the ramp from removed to kept beyond tolerance; 0 = hard edge */
+    float spill;        /* strength of the spill suppression; clamped to [0, 1] by the entry */
+    float spill_range;  /* distance beyond tolerance over which suppression fades to none; 0 = none beyond */
+    int   flags;
+} cvs_chroma_key;
+CVS_EXPORT int cvs_chroma_key_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_chroma_key *key, cvs_stream_t s);
+CVS_EXPORT int cvs_chroma_key_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_chroma_key *key, cvs_stream_t s);
 /* f16 pull of a workspace whose lowest item is a blur node on `source` and whose higher items are `overlays`
  * (bottom first); the blur result stays f32 until the final truncation, as workspace.c:530-544 would have it */
 CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *source, const float *taps, int ntaps,
