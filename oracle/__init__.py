@@ -133,6 +133,85 @@ class flavour:
         return False
 
 
+# ---- the reference's own code, built by oracle/ref_build.py --------------------------------
+
+class coded_image(C.Structure):
+    _fields_ = [("data", C.c_void_p * 4), ("stride", C.c_int * 4), ("line_count", C.c_int * 4), ("free_func", C.c_void_p)]
+
+
+_REF_HALF_POINTERS = {
+    "half_convert_to_float": C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_uint16), C.c_int),
+    "half_convert_from_float": C.CFUNCTYPE(None, C.POINTER(C.c_uint16), C.POINTER(C.c_float), C.c_int),
+    "half_convert_to_float_fast": C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_uint16), C.c_int),
+    "half_convert_from_float_fast": C.CFUNCTYPE(None, C.POINTER(C.c_uint16), C.POINTER(C.c_float), C.c_int),
+    "half_lookup": C.CFUNCTYPE(None, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_int),
+}
+_refs = {}
+
+
+def _bind_ref(lib):
+    P = C.POINTER
+    u16p, vp = P(C.c_uint16), C.c_void_p
+    F16, F32 = P(rgba_frame_f16), P(rgba_frame_f32)
+    sig = {
+        "init_half": (None, []),
+        "video_transfer_rec709_to_linear_scene": (None, [u16p, u16p, C.c_size_t]),
+        "video_transfer_rec709_to_linear_display": (None, [u16p, u16p, C.c_size_t]),
+        "video_transfer_linear_to_rec709": (None, [u16p, u16p, C.c_size_t]),
+        "video_transfer_linear_to_sRGB": (None, [u16p, u16p, C.c_size_t]),
+        "video_get_gamma45_ramp": (P(C.c_uint8), []),
+        "filter_createTriangle": (None, [C.c_float, C.c_float, P(fir_filter)]),
+        "filter_createLanczos": (None, [C.c_float, C.c_int, C.c_float, P(fir_filter)]),
+        "filter_free": (None, [P(fir_filter)]),
+        "video_get_frame_f16": (None, [P(video_source), C.c_int, F16]),
+        "video_get_frame_f32": (None, [P(video_source), C.c_int, F32]),
+        "video_copy_frame_f16": (None, [F16, F16]),
+        "video_copy_frame_alpha_f32": (None, [F32, F32, C.c_float]),
+        "video_mix_cross_f32": (None, [F32, F32, F32, C.c_float]),
+        "video_mix_over_f32": (None, [F32, F32, C.c_float]),
+        "video_scale_bilinear_f32": (None, [F32, v2f, F32, v2f, v2f]),
+        "video_color_rgb_to_xyz_sdtv": (None, [F16]),
+        "video_color_xyz_to_srgb": (None, [F16]),
+        "video_reconstruct_dv": (None, [F16, P(coded_image)]),
+        "video_subsample_dv": (P(coded_image), [F16]),
+        "workspace_create": (vp, []),
+        "workspace_add_item": (vp, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]),
+        "workspace_as_video_source": (None, [vp, P(video_source)]),
+        "workspace_free": (None, [vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    lib.init_half()
+    for name, proto in _REF_HALF_POINTERS.items():
+        setattr(lib, name, proto(C.c_void_p.in_dll(lib, name).value))
+    return lib
+
+
+def ref(flavour="gcc"):
+    """The reference's own src/cprocess, compiled by oracle/ref_build.py ("gcc": libcprocess_ref.so, the build liboracle.so
+    restates; "fma": libcprocess_ref_fma.so, the one liboracle_fma.so restates), bound under the reference's own symbol
+    names with init_half() done and its five half.c pointer globals callable as attributes.  None when the file is absent
+    or does not load (no reference tree where it would have been built): callers skip.  GL entry points are undefined in
+    these files, hence the lazy binding; no CPU path reaches them."""
+    assert flavour in ("gcc", "fma")
+    if flavour not in _refs:
+        from . import ref_build
+        lib = None
+        if os.path.exists(ref_build.path(flavour)):
+            try:
+                lib = _bind_ref(C.CDLL(ref_build.path(flavour), mode=os.RTLD_LAZY))
+            except (OSError, AttributeError):
+                lib = None
+        _refs[flavour] = lib
+    return _refs[flavour]
+
+
+def free_coded_image(image):
+    """Release a coded_image the reference (or anything with its free_func protocol) allocated."""
+    C.CFUNCTYPE(None, C.c_void_p)(image.contents.free_func)(C.cast(image, C.c_void_p))
+
+
 # ---- numpy conveniences -------------------------------------------------------------------
 
 def _u16(a):

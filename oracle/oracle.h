@@ -6,20 +6,21 @@
  * cpu_baseline leg use it, and only as the checker / reported CPU baseline.
  *
  * Pinning status ("how do we know this restatement is right?"):
- *   - The reference hot path cannot be compiled in this image without writing
- *     stand-ins (every file includes framework.h -> <GL/glew.h>, which is
- *     absent, and half.c needs halftab.c, generated by a Python-2 script), so
- *     there is no oracle/_ref build.
+ *   - Where the reference tree is present, oracle/ref_build.py compiles its own
+ *     src/cprocess in place into oracle/_ref/ (gcc and clang flavours), and
+ *     tests/test_oracle_against_reference.py holds every function below that
+ *     has a CPU implementation there to it, bit for bit.
  *   - Pinned by the reference's own known-answer tests: crossfade KAT
  *     (tests/canvas/sequence.py:58-100), solid/window KATs
  *     (tests/process/video/RgbaFrameF16.py:6-23,
  *      tests/process/video/SolidColorVideoSource.py:13-55).
  *   - h2f is additionally checked against IEEE-754 (numpy) for all 65536
  *     codes and f2h against an independent integer round-toward-zero model.
- *   - over / scale / colour-matrix / LUT / FIR values: the reference holds no
- *     test or fixture for them => "parity unpinned" beyond a line-by-line
- *     restatement; Gaussian blur and gain/offset rounding are unpinned even in
- *     principle (no CPU implementation exists in the reference).
+ *   - over / scale / named colour functions / LUT / tap values: the reference
+ *     holds no test or fixture for them; they are pinned by that build.
+ *     Gaussian blur, gain/offset rounding, the general matrix and everything
+ *     else without a CPU implementation in the reference are defined by this
+ *     project alone (Part II A).
  *
  * All file:line citations are relative to /root/reference.
  * Struct layouts follow include/framework.h:46-75,155-213,618-627 so the same
