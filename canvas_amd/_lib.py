@@ -19,6 +19,7 @@ FIR_KERNEL_NONE, FIR_KERNEL_WINDOW, FIR_KERNEL_HALVE, _FIR_KERNEL_RETIRED_3, FIR
 ARITH_SEPARATE, ARITH_CONTRACTED = 0, 1          # cvs_set_arithmetic: the reference's gcc build / its clang (contracting) build
 LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_TO_REC709, LUT_LINEAR_TO_SRGB = -1, 0, 1, 2, 3
 KEY_SHOW_MATTE = 1                                  # cvs_chroma_key.flags
+MATTE_SHOW, MATTE_MAX_CHOKE, MATTE_MAX_TAPS = 1, 16, 25    # cvs_matte.flags and its limits
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
@@ -39,6 +40,20 @@ class chain_job(C.Structure):
 class chroma_key(C.Structure):
     _fields_ = [("key", C.c_float * 3), ("tolerance", C.c_float), ("softness", C.c_float), ("spill", C.c_float),
                 ("spill_range", C.c_float), ("flags", C.c_int)]
+
+
+class matte_params(C.Structure):
+    _fields_ = [("black", C.c_float), ("white", C.c_float), ("choke", C.c_int), ("ntaps", C.c_int), ("taps", C.POINTER(C.c_float)),
+                ("flags", C.c_int)]
+
+
+def matte(choke=0, feather=None, black=0.0, white=1.0, show_matte=False):
+    """A cvs_matte for the two cvs_matte_refine entries; the tap array lives as long as the struct returned."""
+    taps = [float(t) for t in feather] if feather is not None else []
+    array = (C.c_float * len(taps))(*taps) if taps else None
+    m = matte_params(black, white, int(choke), len(taps), C.cast(array, C.POINTER(C.c_float)) if taps else None, MATTE_SHOW if show_matte else 0)
+    m._taps = array
+    return m
 
 
 class coded_image(C.Structure):
@@ -186,6 +201,8 @@ SIGNATURES = {
     "cvs_unsharp_mask_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, C.c_float, C.c_float, _vp]),
     "cvs_chroma_key_f32_dev": (C.c_int, [_F32, _F32, P(chroma_key), _vp]),
     "cvs_chroma_key_f16_dev": (C.c_int, [_F16, _F16, P(chroma_key), _vp]),
+    "cvs_matte_refine_f32_dev": (C.c_int, [_F32, _F32, P(matte_params), _vp]),
+    "cvs_matte_refine_f16_dev": (C.c_int, [_F16, _F16, P(matte_params), _vp]),
     "cvs_blur_over_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, P(_F16), C.c_int, _vp]),
     "cvs_resample_lanczos_f32_dev": (C.c_int, [_F32, _F32, C.c_float, C.c_float, C.c_int, _vp]),
     "cvs_resample_lanczos_f16_dev": (C.c_int, [_F16, _F16, C.c_float, C.c_float, C.c_int, _vp]),

@@ -332,6 +332,26 @@ typedef struct {
 } cvk_key_params;
 int cvk_chroma_key(const cvk_key_params *kp, cvk_view out, cvk_view in, cvk_rect w, int half, int cus, void *stream);
 
+/* Matte refine (matte_ops.hip, DESIGN.md "Matte refine"): levels, choke and feather of the alpha channel in one launch, colour
+ * carried through.  `w` (the window written) inside both views and inside `s`, the source's current window, itself inside `in`;
+ * the views are of one format and NOT the same buffer.  What host/matte.c worked out of a cvs_matte: inv = 1 / (white - black)
+ * (read only where levels != 0), r = |choke| <= 16, grow = choke < 0, ntaps 0 or odd <= 25, and the tile (tw a multiple of 2,
+ * >= 64) whose two LDS images of (tw + 2R) x (th + 2R) floats, R = r + ntaps / 2, must fit CVK_MATTE_MAX_LDS.  The launcher
+ * sets xs.  One arithmetic flavour: every operation is rounded on its own in both (the unit is not rebuilt with -DCVS_CONTRACT). */
+#define CVK_MATTE_MAX_LDS (160u << 10)
+typedef struct {
+    cvk_view out, in;
+    cvk_rect w, s;
+    int xs;                    /* column of the first tile's first pixel: w.x0 or the pair boundary left of it */
+    int tw, th;                /* output tile of one workgroup */
+    int r, grow, ntaps;
+    int levels, show;
+    float black, inv;
+    float taps[25];
+} cvk_matte_params;
+size_t cvk_matte_lds_bytes(int tw, int th, int halo);
+int cvk_matte_refine(const cvk_matte_params *mp, int half, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

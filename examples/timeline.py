@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A small timeline built from the same `fluggo.media.process` objects the Canvas editor creates
 (fluggo/editor/graph/video.py): two clips cut together with a crossfade, a picture-in-picture layer scaled down over
-them, a chroma-keyed layer, a title bar on top.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
+them, a chroma-keyed layer with its matte refined, a title bar on top.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
 
     python examples/timeline.py [out_dir]        # writes frame_000.png ... (and prints Mpx/s)
 """
@@ -56,6 +56,7 @@ pip = process.VideoUnsharpMaskFilter(pip, process.gaussian_taps(1.0, 5), amount=
 # a keyed layer: a 'green-screen shot' (a green ground whose colour drifts towards the subject's orange) loses its ground and its spill
 shot = process.SolidColorVideoSource(process.LerpFunc((0.08, 0.62, 0.12, 1.0), (0.8, 0.45, 0.1, 1.0), FRAMES), box2i(60, 60, 420, 300))
 keyed = process.VideoChromaKeyFilter(shot, key=(0.08, 0.62, 0.12, 1.0), tolerance=0.08, softness=0.25, spill=0.8, spill_range=0.4)
+keyed = process.VideoMatteFilter(keyed, choke=1, feather=process.gaussian_taps(1.0))    # take the rim off the matte, soften its edge
 title = process.SolidColorVideoSource((0.0, 0.0, 0.0, 0.7), box2i(0, H - 90, W - 1, H - 1))
 
 timeline = process.VideoWorkspace()

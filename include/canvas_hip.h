@@ -500,6 +500,36 @@ typedef struct cvs_chroma_key {
 } cvs_chroma_key;
 CVS_EXPORT int cvs_chroma_key_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_chroma_key *key, cvs_stream_t s);
 CVS_EXPORT int cvs_chroma_key_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_chroma_key *key, cvs_stream_t s);
+/* Matte refine (DESIGN.md "Matte refine"): the three controls that follow a keyer -- clip (black and white levels on the
+ * matte), choke (shrink or grow it by whole pixels) and feather (blur the matte only) -- on the alpha channel of un-premultiplied
+ * frames, in one launch; colour is carried through code for code.  S = source.current_window, win = S clipped to
+ * target.full_window; on success target.current_window = win (0 is returned for an empty one too, and nothing is launched), pixels
+ * of `target` outside it keep what they held.  Every stage is defined over the whole of S and the output is its crop to win.
+ * -1 with a message and an empty target window, before the device is touched, for: a NULL frame or a NULL `m`; a source window
+ * outside its full window; |choke| > CVS_MATTE_MAX_CHOKE; ntaps < 0, even, or > CVS_MATTE_MAX_TAPS, ntaps > 0 with NULL taps, a
+ * non-finite tap; non-finite black or white, or white <= black; a bit of flags other than CVS_MATTE_SHOW; target->data ==
+ * source->data (the operation is not in place; partly overlapping buffers are the caller's error and are not detected).
+ * Per pixel, in f32 (a half widened exactly), every operation rounded on its own in both arithmetic flavours, with r = |choke|,
+ * c = (ntaps - 1) / 2 and inv = 1.0f / (white - black):
+ *     a0 = s.a, a NaN alpha counting as 0
+ *     a1 = (black == 0 && white == 1) ? a0 : ramp((a0 - black) * inv)         ramp(t) = (t < 1) ? ((t > 0) ? t : 0) : 1
+ *     a2(x, y) = choke > 0 ? min : choke < 0 ? max : identity  of a1 over {(x+i, y+j) : |i| <= r, |j| <= r} clipped to S
+ *                (samples outside S are skipped, not taken as transparent)
+ *     h(x, y)  = t after: t = 0; for k = 0 .. ntaps-1: if (x+k-c, y) in S: p = a2(x+k-c, y) * taps[k]; t = t + p
+ *     a3(x, y) = t after: t = 0; for k = 0 .. ntaps-1: if (x, y+k-c) in S: p = h(x, y+k-c) * taps[k]; t = t + p      (ntaps == 0: a2)
+ *     out = (flags & CVS_MATTE_SHOW) ? (a3, a3, a3, 1) : (s.r, s.g, s.b, a3)
+ * f16 targets are truncated once, at the store.  The sign of a zero that a minimum or maximum returns is not pinned. */
+enum { CVS_MATTE_SHOW = 1 };
+enum { CVS_MATTE_MAX_CHOKE = 16, CVS_MATTE_MAX_TAPS = 25 };
+typedef struct cvs_matte {
+    float black, white;   /* matte levels: alpha <= black -> 0, >= white -> 1; 0 and 1 switch the stage off */
+    int   choke;          /* > 0 shrinks the matte (minimum over a square), < 0 grows it (maximum); |choke| <= 16 */
+    int   ntaps;          /* feather: 0 = none, else an odd count 1..25 of finite taps, normalised by the caller */
+    const float *taps;    /* host pointer */
+    int   flags;
+} cvs_matte;
+CVS_EXPORT int cvs_matte_refine_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_matte *m, cvs_stream_t s);
+CVS_EXPORT int cvs_matte_refine_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_matte *m, cvs_stream_t s);
 /* f16 pull of a workspace whose lowest item is a blur node on `source` and whose higher items are `overlays`
  * (bottom first); the blur result stays f32 until the final truncation, as workspace.c:530-544 would have it */
 CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *source, const float *taps, int ntaps,
