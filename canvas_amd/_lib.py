@@ -20,6 +20,7 @@ ARITH_SEPARATE, ARITH_CONTRACTED = 0, 1          # cvs_set_arithmetic: the refer
 LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_TO_REC709, LUT_LINEAR_TO_SRGB = -1, 0, 1, 2, 3
 KEY_SHOW_MATTE = 1                                  # cvs_chroma_key.flags
 MATTE_SHOW, MATTE_MAX_CHOKE, MATTE_MAX_TAPS = 1, 16, 25    # cvs_matte.flags and its limits
+TRANSFORM_NEAREST, TRANSFORM_BILINEAR, TRANSFORM_MAX_COORD = 0, 1, 1 << 23    # cvs_transform.filter and the coordinate limit
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
@@ -54,6 +55,15 @@ def matte(choke=0, feather=None, black=0.0, white=1.0, show_matte=False):
     m = matte_params(black, white, int(choke), len(taps), C.cast(array, C.POINTER(C.c_float)) if taps else None, MATTE_SHOW if show_matte else 0)
     m._taps = array
     return m
+
+
+class transform_params(C.Structure):
+    _fields_ = [("m", C.c_float * 6), ("filter", C.c_int), ("flags", C.c_int)]
+
+
+def transform(m=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0), filter=TRANSFORM_BILINEAR):
+    """A cvs_transform for the two cvs_transform entries and the window helpers: m maps target to source coordinates."""
+    return transform_params((C.c_float * 6)(*[float(v) for v in m]), int(filter), 0)
 
 
 class coded_image(C.Structure):
@@ -203,6 +213,11 @@ SIGNATURES = {
     "cvs_chroma_key_f16_dev": (C.c_int, [_F16, _F16, P(chroma_key), _vp]),
     "cvs_matte_refine_f32_dev": (C.c_int, [_F32, _F32, P(matte_params), _vp]),
     "cvs_matte_refine_f16_dev": (C.c_int, [_F16, _F16, P(matte_params), _vp]),
+    "cvs_transform_f32_dev": (C.c_int, [_F32, _F32, P(transform_params), _vp]),
+    "cvs_transform_f16_dev": (C.c_int, [_F16, _F16, P(transform_params), _vp]),
+    "cvs_transform_from_parts": (C.c_int, [P(C.c_double), P(C.c_double), C.c_double, P(C.c_double), _f32p]),
+    "cvs_transform_target_window": (C.c_int, [P(transform_params), P(box2i), P(box2i), P(box2i)]),
+    "cvs_transform_source_window": (C.c_int, [P(transform_params), P(box2i), P(box2i)]),
     "cvs_blur_over_f16_dev": (C.c_int, [_F16, _F16, _f32p, C.c_int, P(_F16), C.c_int, _vp]),
     "cvs_resample_lanczos_f32_dev": (C.c_int, [_F32, _F32, C.c_float, C.c_float, C.c_int, _vp]),
     "cvs_resample_lanczos_f16_dev": (C.c_int, [_F16, _F16, C.c_float, C.c_float, C.c_int, _vp]),

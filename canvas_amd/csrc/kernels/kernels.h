@@ -352,6 +352,20 @@ typedef struct {
 size_t cvk_matte_lds_bytes(int tw, int th, int halo);
 int cvk_matte_refine(const cvk_matte_params *mp, int half, void *stream);
 
+/* Affine transform (transform_ops.hip, DESIGN.md "Affine transform"): `w` (the window written) inside `out`, `s` (the source's
+ * current window, not empty) inside `in`; the views are of one format and NOT the same buffer; every coordinate of `w` and `s`
+ * within +-2^23.  m maps target to source coordinates.  The tile of one 256-lane workgroup is tw x th target pixels, tw a power
+ * of two from 8 to 256 and tw * th == 256 (host/transform.c plans it). */
+typedef struct {
+    cvk_view out, in;
+    cvk_rect w, s;
+    float m[6];
+    int bilinear;              /* else nearest */
+    int tw, th;
+    int pair_loads;            /* read only by the diagnostic build: the two horizontal taps of a half pixel in one 16-byte load */
+} cvk_transform_params;
+int cvk_transform(const cvk_transform_params *tp, int half, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

@@ -58,12 +58,17 @@ shot = process.SolidColorVideoSource(process.LerpFunc((0.08, 0.62, 0.12, 1.0), (
 keyed = process.VideoChromaKeyFilter(shot, key=(0.08, 0.62, 0.12, 1.0), tolerance=0.08, softness=0.25, spill=0.8, spill_range=0.4)
 keyed = process.VideoMatteFilter(keyed, choke=1, feather=process.gaussian_taps(1.0))    # take the rim off the matte, soften its edge
 title = process.SolidColorVideoSource((0.0, 0.0, 0.0, 0.7), box2i(0, H - 90, W - 1, H - 1))
+# a second picture in picture that turns: a card at 40 % size spinning about its own centre, its edges keeping their colour
+card = process.SolidColorVideoSource((0.2, 0.85, 0.9, 0.9), box2i(0, 0, 479, 269))
+card = process.VideoTransformFilter(card, box2i(0, 0, 479, 269), anchor=(239.5, 134.5), scale=(0.4, 0.4),
+                                    rotation=process.LerpFunc((0.0,), (180.0,), FRAMES), position=(160, 120))
 
 timeline = process.VideoWorkspace()
 timeline.add(source=sequence, x=0, length=FRAMES, z=0, offset=0)
 timeline.add(source=pip, x=10, length=40, z=1, offset=0)
 timeline.add(source=keyed, x=0, length=FRAMES, z=2, offset=0)
 timeline.add(source=title, x=0, length=FRAMES, z=3, offset=0)
+timeline.add(source=card, x=0, length=FRAMES, z=4, offset=0)
 
 window = box2i(0, 0, W - 1, H - 1)
 timeline.get_frame_rgba8(0, window)                       # first use: tables, code objects

@@ -530,6 +530,50 @@ typedef struct cvs_matte {
 } cvs_matte;
 CVS_EXPORT int cvs_matte_refine_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_matte *m, cvs_stream_t s);
 CVS_EXPORT int cvs_matte_refine_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_matte *m, cvs_stream_t s);
+/* Affine transform (DESIGN.md "Affine transform"): rotate, scale, mirror and move a layer of un-premultiplied pixels, the
+ * bilinear filter weighted by alpha so that a layer's edge keeps its colour and only its alpha falls off.  Integer coordinates
+ * are sample positions.  `m` maps TARGET coordinates to SOURCE coordinates.  S = source.current_window; the entry writes
+ * win = cvs_transform_target_window(t, S, target.full_window) and sets target.current_window = win (0 is returned for an empty
+ * one too, and nothing is launched); pixels of `target` outside win keep what they held.  The output is the crop of the
+ * infinite-plane result to win.
+ * -1 with a message and an empty target window, before the device is touched, for: a NULL frame or a NULL `t`; a source window
+ * outside its full window; a filter other than the two; flags != 0; a non-finite m[k]; m0*m4 - m1*m3 (in double) zero or not
+ * finite; a coordinate of S or of target.full_window beyond +-CVS_TRANSFORM_MAX_COORD (every coordinate is then an exact
+ * float); target->data == source->data.
+ * Per pixel, in f32 (a half widened exactly), every operation rounded on its own in both arithmetic flavours:
+ *     x, y = (float) of the target pixel's coordinates
+ *     u = (m0*x + m1*y) + m2 ;  v = (m3*x + m4*y) + m5
+ *     in(i, j) = S.min.x <= i <= S.max.x and S.min.y <= j <= S.max.y, compared as floats (false for NaN and +-Inf)
+ *     NEAREST:   i = floorf(u + 0.5f), j = floorf(v + 0.5f);  out = in(i, j) ? source(i, j) code for code : (0, 0, 0, 0)
+ *     BILINEAR:  i = floorf(u), j = floorf(v);  a = u - i;  b = v - j;  wa = 1 - a;  wb = 1 - b
+ *                a == 0 and b == 0 (on a sample):  out = in(i, j) ? source(i, j) code for code : (0, 0, 0, 0)
+ *                else A = R = G = B = 0;  for (w, di, dj) in (wa*wb, 0, 0), (a*wb, 1, 0), (wa*b, 0, 1), (a*b, 1, 1), in this order:
+ *                         if in(i + di, j + dj):  p = source(i + di, j + dj);  q = w * p.a;  A = A + q;
+ *                                                 R = R + q*p.r;  G = G + q*p.g;  B = B + q*p.b
+ *                     out = A != 0 ? (R / A, G / A, B / A, A) : (0, 0, 0, 0)
+ * Taps outside S are skipped and never read.  f16 targets are truncated once, at the store (the copy paths move the code).  The
+ * payload of a NaN is not pinned. */
+enum { CVS_TRANSFORM_NEAREST = 0, CVS_TRANSFORM_BILINEAR = 1 };
+enum { CVS_TRANSFORM_MAX_COORD = 1 << 23 };
+typedef struct cvs_transform {
+    float m[6];     /* TARGET -> SOURCE:  u = (m[0]*x + m[1]*y) + m[2];   v = (m[3]*x + m[4]*y) + m[5] */
+    int   filter;
+    int   flags;    /* none defined: must be 0 */
+} cvs_transform;
+CVS_EXPORT int cvs_transform_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_transform *t, cvs_stream_t s);
+CVS_EXPORT int cvs_transform_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_transform *t, cvs_stream_t s);
+/* Pure host arithmetic in double, no device needed.
+ * _from_parts: the coefficients of the layer transform  target = position + R(rotation) * diag(scale) * (p - anchor), rotation
+ * in degrees, clockwise on screen (y down), multiples of 90 degrees exact; inverted and rounded to f32 once.  0 on success,
+ * 1 with `m` untouched when a scale is exactly 0 (degenerate: nothing to draw), -1 with a message for a non-finite input or
+ * result.
+ * _target_window: the target pixels that can have a tap inside `source_current`, clipped to `target_full` (DESIGN.md has the
+ * formula).  _source_window: the source pixels the taps of `target_window` can touch.  Both return 0, or -1 with a message and
+ * an empty box for a NULL argument, a filter other than the two, a non-finite coefficient or a determinant that is zero or not
+ * finite. */
+CVS_EXPORT int cvs_transform_from_parts(const double anchor[2], const double scale[2], double rotation_degrees, const double position[2], float m[6]);
+CVS_EXPORT int cvs_transform_target_window(const cvs_transform *t, const box2i *source_current, const box2i *target_full, box2i *win);
+CVS_EXPORT int cvs_transform_source_window(const cvs_transform *t, const box2i *target_window, box2i *need);
 /* f16 pull of a workspace whose lowest item is a blur node on `source` and whose higher items are `overlays`
  * (bottom first); the blur result stays f32 until the final truncation, as workspace.c:530-544 would have it */
 CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *source, const float *taps, int ntaps,
