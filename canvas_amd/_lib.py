@@ -158,6 +158,7 @@ SIGNATURES = {
     "cvs_pool_malloc": (_vp, [C.c_size_t, _vp]),
     "cvs_pool_free": (None, [_vp, _vp]),
     "cvs_pool_trim": (None, []),
+    "cvs_thread_release": (None, []),
     "cvs_memcpy_h2d": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "cvs_memcpy_d2h": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "cvs_memcpy_d2d": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

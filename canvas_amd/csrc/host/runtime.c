@@ -211,6 +211,22 @@ hipStream_t cvs_pick_stream(cvs_stream_t s) {
     return t_streams[t_ctx];
 }
 
+/* A thread that is about to end gives back the stream it was lent in every context it called into (nothing does it for a thread:
+ * a pull-queue worker that simply returned left its stream, and the device memory the runtime keeps per stream, behind -- four
+ * workers, 16 MiB per queue).  What the thread queued is waited for first; parked pool blocks name their stream only to compare
+ * it and order themselves by their events, so a destroyed handle does no harm there. */
+CVS_EXPORT void cvs_thread_release(void) {
+    for (int i = 0; i < CVS_MAX_CONTEXTS; i++) {
+        if (!t_have_stream[i]) continue;
+        if (t_streams[i] && hipSetDevice(g_ctx[i].device) == hipSuccess) {
+            (void)hipStreamSynchronize(t_streams[i]);
+            (void)hipStreamDestroy(t_streams[i]);
+        }
+        t_streams[i] = NULL;
+        t_have_stream[i] = 0;
+    }
+}
+
 CVS_EXPORT void *cvs_malloc(size_t bytes) {
     void *p = NULL;
     if (cvs_enter() != 0) return NULL;

@@ -9,8 +9,8 @@
  * parts are numbers, pairs or frame functions, read as f32 like every v2f of the path; cvs_transform_from_parts turns them into the
  * six target -> source coefficients, which inverse_at(frame_index) shows.  source_rect bounds what is pulled, as VideoScaler's
  * does: the source is pulled over cvs_transform_source_window(the frame asked for) clipped to it into a pooled frame, then the
- * entry of the pulled format writes the frame.  Coordinates are absolute, so a frame pulled in tiles equals the frame pulled
- * whole.  f32 is the node's own format; an f16 pull over a half-native source goes through the _f16_dev entry in one launch
+ * entry of the pulled format writes the frame; the window reported is where source_rect lands in the frame asked for (fill_layer).
+ * Coordinates are absolute, so a frame pulled in tiles equals the frame pulled whole, window included.  f32 is the node's own format; an f16 pull over a half-native source goes through the _f16_dev entry in one launch
  * (pymatte.c).  Locking as in pymatte.c: reader lock around the upstream pull and the parameters, writer lock where either is
  * replaced.  A pull never raises: no source, no device, a degenerate scale or a refusing entry end in an empty window.
  */
@@ -107,18 +107,53 @@ static int coefficients(py_transform *self, int frame_index, float m[6]) {
     return cvs_transform_from_parts(a, s, framefunc_get_f32(&self->part[PART_ROTATION], frame_index), p, m);
 }
 
+/* transparent black over `box` of `f` (its window is left alone): 0, or -1 */
+static int clear_box(rgba_frame_dev *f, int x0, int y0, int x1, int y1) {
+    static const rgba_f32 nothing = { 0.0f, 0.0f, 0.0f, 0.0f };
+    box2i box;
+    box2i_set(&box, x0, y0, x1, y1);
+    if (box2i_is_empty(&box)) return 0;
+    if (f->format == CVS_FORMAT_F16) {
+        rgba_frame_f16 t = { f->data, f->full_window, f->full_window };
+        return cvs_fill_solid_f16_dev(&t, &box, &nothing, f->stream);
+    }
+    rgba_frame_f32 t = { f->data, f->full_window, f->full_window };
+    return cvs_fill_solid_f32_dev(&t, &box, &nothing, f->stream);
+}
+
+/* The window the node reports does not depend on how much of the source this pull happened to ask for: it is where source_rect
+ * lands in the frame asked for, `layer`, of which the entry has written `win` (the part the pulled source reaches); the rest is
+ * transparent black.  With the entry's own window a node above would see a window that varies with the tile it is pulled in, and
+ * a blur's or a matte's result would vary with it (DESIGN.md "Affine transform", Node).  0, or -1 */
+static int fill_layer(rgba_frame_dev *f, const box2i *layer) {
+    box2i win = f->current_window, all = *layer;
+    if (box2i_is_empty(&all)) return 0;
+    if (box2i_is_empty(&win)) { f->current_window = all; return clear_box(f, all.min.x, all.min.y, all.max.x, all.max.y); }
+    if (win.min.x < all.min.x) all.min.x = win.min.x;
+    if (win.min.y < all.min.y) all.min.y = win.min.y;
+    if (win.max.x > all.max.x) all.max.x = win.max.x;
+    if (win.max.y > all.max.y) all.max.y = win.max.y;
+    f->current_window = all;
+    if (clear_box(f, all.min.x, all.min.y, all.max.x, win.min.y - 1) != 0 || clear_box(f, all.min.x, win.max.y + 1, all.max.x, all.max.y) != 0) return -1;
+    if (clear_box(f, all.min.x, win.min.y, win.min.x - 1, win.max.y) != 0 || clear_box(f, win.max.x + 1, win.min.y, all.max.x, win.max.y) != 0) return -1;
+    return 0;
+}
+
 /* `f` in either format: the source pulled in that format over the window the taps need, then the library entry of that format */
 static void transform_render(PyObject *o, int frame_index, rgba_frame_dev *f) {
     py_transform *self = (py_transform *)o;
     py_rdlock(&self->n.lock);
     cvs_transform t = { { 0 }, self->filter, 0 };
-    box2i need, rect;
+    box2i need, rect, layer = { { 0, 0 }, { -1, -1 } };
     rgba_frame_dev in = { NULL, f->format, { { 0, 0 }, { -1, -1 } }, { { 0, 0 }, { -1, -1 } }, f->stream };
-    bool draw = coefficients(self, frame_index, t.m) == 0 && cvs_transform_source_window(&t, &f->full_window, &need) == 0;
+    const bool sound = coefficients(self, frame_index, t.m) == 0 && cvs_transform_source_window(&t, &f->full_window, &need) == 0;
+    bool draw = sound, beyond = false;            /* beyond: the frame asked for reaches nothing of source_rect */
     if (draw && self->n.source) {
         framefunc_get_box2i(&rect, &self->part[PART_RECT], frame_index);
+        if (cvs_transform_target_window(&t, &rect, &f->full_window, &layer) != 0) box2i_set_empty(&layer);
         box2i_intersect(&need, &need, &rect);
-        draw = !box2i_is_empty(&need);
+        beyond = box2i_is_empty(&need);
+        draw = !beyond;
     }
     if (draw && self->n.source) {
         const int lim = CVS_TRANSFORM_MAX_COORD;
@@ -142,7 +177,12 @@ static void transform_render(PyObject *o, int frame_index, rgba_frame_dev *f) {
             rc = cvs_transform_f32_dev(&fo, self->n.source ? &fi : NULL, &t, f->stream);
             f->current_window = fo.current_window;
         }
+    } else if (beyond) {
+        /* the entry has nothing to write; the layer's box is still reported */
+        rc = 0;
+        box2i_set_empty(&f->current_window);
     }
+    if (rc == 0 && self->n.source) rc = fill_layer(f, &layer);
     pthread_rwlock_unlock(&self->n.lock);
     if (rc != 0) box2i_set_empty(&f->current_window);
     if (in.data) cvs_pool_free(in.data, f->stream);

@@ -207,6 +207,7 @@ typedef struct {
     py_pq_item *head[PQ_MAX], *tail[PQ_MAX];       /* one list per device context of the queue (one in all without `devices`) */
     int nctx;                                       /* lists in use */
     int ctx[PQ_MAX];                                /* the library's context id of each (-1: the default context) */
+    int dev[PQ_MAX];                                /* and its HIP device */
     int quit, refs;
 } pq_core;
 
@@ -222,11 +223,35 @@ typedef struct {
 
 static PyTypeObject py_type_PullQueueItem;
 
+/* The library never closes a device context, and what a context holds on its device (tap and transfer tables, parked scratch)
+ * stays with it.  A queue that has gone therefore leaves its contexts here, and the next queue that names the same device takes
+ * them over instead of opening more: a host that makes a queue per playback neither runs out of contexts nor grows on the device. */
+static pthread_mutex_t idle_lock = PTHREAD_MUTEX_INITIALIZER;
+static struct { int ctx, device; } idle_contexts[PQ_MAX * 4];
+static int idle_count;
+
+static int context_take(int device) {
+    int ctx = -1;
+    pthread_mutex_lock(&idle_lock);
+    for (int i = 0; i < idle_count && ctx < 0; i++)
+        if (idle_contexts[i].device == device) { ctx = idle_contexts[i].ctx; idle_contexts[i] = idle_contexts[--idle_count]; }
+    pthread_mutex_unlock(&idle_lock);
+    return ctx >= 0 ? ctx : cvs_context_open(device);
+}
+static void context_give(int ctx, int device) {
+    pthread_mutex_lock(&idle_lock);
+    if (idle_count < (int)(sizeof idle_contexts / sizeof idle_contexts[0])) { idle_contexts[idle_count].ctx = ctx; idle_contexts[idle_count].device = device; idle_count++; }
+    pthread_mutex_unlock(&idle_lock);
+}
+
 static void pq_core_unref(pq_core *c) {
     pthread_mutex_lock(&c->mutex);
     const int left = --c->refs;
     pthread_mutex_unlock(&c->mutex);
-    if (left == 0) { pthread_cond_destroy(&c->wake); pthread_mutex_destroy(&c->mutex); free(c); }
+    if (left == 0) {                                        /* every worker has left: nobody runs in the contexts any more */
+        for (int i = 0; i < c->nctx; i++) if (c->ctx[i] >= 0) context_give(c->ctx[i], c->dev[i]);
+        pthread_cond_destroy(&c->wake); pthread_mutex_destroy(&c->mutex); free(c);
+    }
 }
 
 static void *pq_worker(void *arg) {
@@ -237,7 +262,13 @@ static void *pq_worker(void *arg) {
     for (;;) {
         pthread_mutex_lock(&q->mutex);
         while (!q->head[me] && !q->quit) pthread_cond_wait(&q->wake, &q->mutex);
-        if (!q->head[me] && q->quit) { pthread_mutex_unlock(&q->mutex); pq_core_unref(q); return NULL; }
+        if (!q->head[me] && q->quit) {
+            pthread_mutex_unlock(&q->mutex);
+            if (q->ctx[me] >= 0) cvs_pool_trim();           /* the scratch parked in the queue's own context goes back to the driver */
+            cvs_thread_release();                           /* and this thread's streams */
+            pq_core_unref(q);
+            return NULL;
+        }
         py_pq_item *it = q->head[me];
         q->head[me] = it->next;
         if (!q->head[me]) q->tail[me] = NULL;
@@ -295,9 +326,14 @@ static int pq_init(py_pullqueue *self, PyObject *args, PyObject *kw) {
     self->devices[0] = -1;
     if (ndev) {
         for (int i = 0; i < ndev; i++) {
-            c->ctx[i] = cvs_context_open(dev[i]);
-            self->devices[i] = dev[i];
-            if (c->ctx[i] < 0) { free(c); PyErr_Format(PyExc_RuntimeError, "VideoPullQueue: no context on device %d: %s", dev[i], cvs_last_error()); return -1; }
+            c->ctx[i] = context_take(dev[i]);
+            c->dev[i] = self->devices[i] = dev[i];
+            if (c->ctx[i] < 0) {
+                for (int k = 0; k < i; k++) context_give(c->ctx[k], c->dev[k]);
+                free(c);
+                PyErr_Format(PyExc_RuntimeError, "VideoPullQueue: no context on device %d: %s", dev[i], cvs_last_error());
+                return -1;
+            }
         }
         c->nctx = ndev;
     }

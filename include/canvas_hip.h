@@ -290,6 +290,8 @@ CVS_EXPORT int cvs_mem_info(size_t *free_bytes, size_t *total_bytes);     /* HBM
 CVS_EXPORT void *cvs_pool_malloc(size_t bytes, cvs_stream_t s);
 CVS_EXPORT void cvs_pool_free(void *dev, cvs_stream_t s);
 CVS_EXPORT void cvs_pool_trim(void);
+/* for a thread that is about to end: waits for what it queued and destroys the stream it was lent in each context */
+CVS_EXPORT void cvs_thread_release(void);
 CVS_EXPORT int cvs_memcpy_h2d(void *dev, const void *host, size_t bytes, cvs_stream_t s);
 CVS_EXPORT int cvs_memcpy_d2h(void *host, const void *dev, size_t bytes, cvs_stream_t s);
 CVS_EXPORT int cvs_memcpy_d2d(void *dst, const void *src, size_t bytes, cvs_stream_t s);

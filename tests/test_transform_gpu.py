@@ -286,11 +286,15 @@ def _canvas(buffer, full, win):
 
 def _node_model(pixels, raster, rect, m, filt, full):
     """What a pull over `full` gives: the source holds `pixels` over `raster`, the node pulls it over the window the taps need,
-    clipped to source_rect -> (pixels over full, zero outside the window; the window)"""
+    clipped to source_rect, and reports where source_rect lands in `full` (transparent black where the entry wrote nothing), so
+    that the window does not depend on the tile -> (pixels over full, zero outside the window; the window)"""
     need = tm.intersect(tm.source_window(m, full), rect)
     S = None if need is None else tm.intersect(need, raster)
     out, win = tm.expected(np.zeros(_box(full) + (4,), pixels.dtype), full, pixels, raster, S, m, filt)
-    return out, win
+    layer = tm.target_window(m, filt, rect, full)
+    if win is not None and layer is not None:
+        layer = (min(win[0], layer[0]), min(win[1], layer[1]), max(win[2], layer[2]), max(win[3], layer[3]))
+    return out, (win if layer is None else layer)
 
 
 def _as_f32(parts):
