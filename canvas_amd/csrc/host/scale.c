@@ -239,7 +239,12 @@ static int triangle_fused_vh(any_frame *target, v2f tp, const any_frame *source,
             const bool tiles = hhi >= hlo && !(pinned & CVS_FIR_PATH_STRIPS) &&
                                ((pinned & CVS_FIR_PATH_TILES) ? CVK(cvk_fir_tvh_supported)(&fp)
                                 : batch && target->half ? false : CVK(cvk_fir_tvh_preferred)(&fp));
-            if (batch && !(hhi >= hlo && (tiles || CVK(cvk_fir_vh_supported)(&fp)))) rc = 2;
+            /* the kernels' predicates (and the instance k_fir_vh picks) look at the target's base address -- a pair of halfs is
+             * ONE 16-byte store -- and fp.target is frame 0: every frame of the launch must answer as frame 0 does, which with
+             * one geometry means the same address modulo 16.  Else the frames run one by one. */
+            bool alike = true;
+            for (int i = 0; batch && i < batch->n; i++) alike = alike && !((((uintptr_t)batch->target[i]) ^ (uintptr_t)target->data) & 15u);
+            if (batch && !(alike && hhi >= hlo && (tiles || CVK(cvk_fir_vh_supported)(&fp)))) rc = 2;
             else if (hhi >= hlo && (tiles || CVK(cvk_fir_vh_supported)(&fp))) {
                 /* video_scale.c:25-32,44: rows the pass leaves alone are zeros */
                 const bool covers = lo2 == tf->min.y && hi2 == tf->max.y;

@@ -53,7 +53,22 @@ typedef struct { float r, g, b, a; } rgba_f32; /* 16 bytes */
 
 /* A frame is a caller-owned buffer covering full_window (rows packed, stride = its width);
  * the callee fills some sub-rectangle and reports it in current_window.  Pixels outside
- * current_window are undefined. */
+ * current_window are undefined.
+ *
+ * Where `data` may lie (device and host entries alike; tests/test_placement_gpu.py holds every windowed cvs_*_dev entry to
+ * it on frames packed into one arena):
+ *   - `data` may be ANY address aligned to one pixel: 8 bytes for rgba_frame_f16, 16 bytes for rgba_frame_f32.  Nothing more
+ *     is asked -- a ring of odd-width half frames packed back to back puts every second one at 8 modulo 16, and that is a
+ *     legal frame.  Where a kernel has a form that moves two half pixels as one 16-byte access, the library looks at the
+ *     address (and at the pitch and the window's first column) and takes that form only where every such access is aligned;
+ *     the pixels are the same either way.
+ *   - coded planes (coded_image.data[]) and the byte targets of cvs_frame_to_bytes_dev / cvs_frame_to_rgba8_intent_dev take
+ *     any address of their element type: any byte address for planes, 4 bytes for the 32-bit display pixels.
+ *   - no entry reads or writes a byte outside the buffers it is handed: full_window's width * height pixels from `data`,
+ *     stride * line_count bytes of a plane, the current window's pixel count * 4 bytes of a byte target.  What lies around a
+ *     frame may be another frame.
+ *   - an address below the pixel's alignment (a half frame at 2 modulo 8, a float frame at 4 modulo 16) is outside the
+ *     contract. */
 typedef struct { rgba_f16 *data; box2i full_window; box2i current_window; } rgba_frame_f16;
 typedef struct { rgba_f32 *data; box2i full_window; box2i current_window; } rgba_frame_f32;
 

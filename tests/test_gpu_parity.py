@@ -2231,6 +2231,39 @@ def test_scale_batch_falls_back_on_mixed_geometry_and_overlap(cvs, orc):
     assert np.array_equal(outs[0].download().array, ones[2].download().array)
     for d in srcs + outs + ones:
         d.free()
+    # three wide f16 frames of one geometry packed into an arena, the second target 8 bytes off the 16-byte grid: the kernels'
+    # two-pixels-per-lane forms store a pair of halfs as ONE 16-byte access and their predicates were asked about frame 0
+    # only, so such a batch must run frame by frame -- every frame its single call, nothing written outside the frames
+    from tests import arena as ar
+    sfull, tfull = (0, 0, 514, 6), (0, 0, 1025, 8)
+    wide = [rand_f16_frame(rng, sfull, sfull) for _ in range(3)]
+    singles = []
+    for f in wide:
+        d_src, d_one = DeviceFrame.from_host(f), DeviceFrame.from_host(HostFrame(tfull, np.uint16, fill=0x1234))
+        _lib.check(cvs.cvs_scale_bilinear_f16_dev(d_one.ref(), v2f(0, 0), d_src.ref(), v2f(0, 0), v2f(2.0, 2.0), None))
+        singles.append(d_one.download())
+        d_src.free(); d_one.free()
+    guard = ar.guard_bytes([1026 * 8])
+    arena = ar.Arena(cvs, ar.capacity_for([515 * 7 * 8] * 3 + [1026 * 9 * 8] * 3, guard), guard)
+    try:
+        for name, poison in ar.POISONS:
+            for residues in [(0, 8, 0), (8, 0, 0), (0, 0, 8), (0, 0, 0), (8, 8, 8)]:
+                arena.fill(poison)
+                a_src = [arena.place(sfull, np.uint16, 0, name="source %d" % k) for k in range(3)]
+                a_out = [arena.place(tfull, np.uint16, r, name="target %d" % k) for k, r in enumerate(residues)]
+                for d, f in zip(a_src, wide):
+                    arena.upload(d.placed, f.array, is_input=True)
+                for d in a_out:
+                    arena.upload(d.placed, np.full((9, 1026, 4), 0x1234, np.uint16), is_input=False)
+                _lib.check(cvs.cvs_scale_bilinear_f16_batch_dev(tab(a_out), v2f(0, 0), tab(a_src), v2f(0, 0), v2f(2.0, 2.0), 3, None))
+                arena.download()
+                arena.check()
+                for k, d in enumerate(a_out):
+                    assert same_window(d.current_window, singles[k].current_window), (residues, k)
+                    assert_same_f16(arena.read(d.placed, np.uint16).reshape(9, 1026, 4), singles[k].array,
+                                    "batch frame %d, targets at %r modulo 256, %s poison" % (k, residues, name))
+    finally:
+        arena.free()
 
 
 def test_tile_scaler_random_geometry(cvs, orc):
