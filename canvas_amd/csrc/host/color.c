@@ -220,6 +220,16 @@ CVS_EXPORT int cvs_mix_cross_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *
     /* each input as its f32 pull would deliver it: clipped to the output's buffer, then widened */
     rgba_frame_f16 clip = { cvs_pool_malloc(n * sizeof(rgba_f16), s), *fw, *fw };
     if (!clip.data) rc = -1;
+    /* Outside its window a widened input is zero, not what the pool block held before, and so is the f32 result where the
+     * crossfade writes nothing: where its `left` selector picks the other frame (video_mix.c:137) the f32 crossfade addresses pixels
+     * outside the windows, and between two windows that do not meet it leaves part of the reported window unwritten.  The result
+     * must not depend on which block the pool happened to hand out (tests/test_graph_replay_gpu.py: a graph keeps the warm run's blocks, so the next
+     * direct call got others, and other pixels). */
+    if (rc == 0 && (hipMemsetAsync(fa.data, 0, n * sizeof(rgba_f32), s) != hipSuccess || hipMemsetAsync(fb.data, 0, n * sizeof(rgba_f32), s) != hipSuccess ||
+                    hipMemsetAsync(fo.data, 0, n * sizeof(rgba_f32), s) != hipSuccess)) {
+        cvs_set_error("cvs_mix_cross_f16_dev: clearing the scratch frames failed");
+        rc = -1;
+    }
     if (rc == 0) rc = cvs_copy_frame_f16_dev(&clip, a, s);
     if (rc == 0) rc = cvs_frame_f16_to_f32_dev(&fa, &clip, s);
     if (rc == 0) rc = cvs_copy_frame_f16_dev(&clip, b, s);

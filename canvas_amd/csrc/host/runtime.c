@@ -306,7 +306,10 @@ CVS_EXPORT int cvs_stream_sync(cvs_stream_t s) {
  * slightly different size every frame); when the table is full the least recently parked block is evicted. */
 #define GRAPH_BLOCKS 64
 typedef struct { void (*release)(void *); void *arg; } cvs_hold;
-static __thread struct { int active, overflow; hipStream_t stream; void *blocks[GRAPH_BLOCKS]; int n; cvs_hold holds[GRAPH_BLOCKS]; int nholds; } t_capture;
+/* `spill`: blocks freed under a capture that already holds GRAPH_BLOCKS of them.  That capture is lost (`overflow`), but the
+ * blocks are not: cvs_graph_end gives them back to the pool with the rest (the first version dropped them, live for ever). */
+static __thread struct { int active, overflow; hipStream_t stream; void *blocks[GRAPH_BLOCKS]; int n; cvs_hold holds[GRAPH_BLOCKS]; int nholds;
+                         void **spill; int nspill, spill_room; } t_capture;
 /* the pool of the context the calling thread's call runs in (g_lock covers every context's table) */
 #define g_pool (g_ctx[t_ctx].pool)
 #define g_pool_clock (g_ctx[t_ctx].pool_clock)
@@ -381,13 +384,27 @@ int cvs_capture_hold(hipStream_t st, void (*release)(void *), void *arg) {
     return 0;
 }
 
-CVS_EXPORT void cvs_pool_free(void *dev, cvs_stream_t s) {
-    if (!dev || cvs_enter() != 0) return;
-    hipStream_t st = cvs_pick_stream(s);
+/* in the context the calling thread is in (t_ctx) */
+static void pool_free_here(void *dev, hipStream_t st) {
     if (t_capture.active && st == t_capture.stream) {
         /* the captured kernels will use this block at every replay: it stays out of the pool, owned by the graph */
-        if (t_capture.n < GRAPH_BLOCKS) t_capture.blocks[t_capture.n++] = dev;
-        else t_capture.overflow = 1;
+        if (t_capture.n < GRAPH_BLOCKS) { t_capture.blocks[t_capture.n++] = dev; return; }
+        t_capture.overflow = 1;                    /* this capture will fail; the block still has to outlive it */
+        if (t_capture.nspill == t_capture.spill_room) {
+            const int room = t_capture.spill_room ? 2 * t_capture.spill_room : GRAPH_BLOCKS;
+            void **more = realloc(t_capture.spill, sizeof(void *) * (size_t)room);
+            if (more) { t_capture.spill = more; t_capture.spill_room = room; }
+        }
+        if (t_capture.nspill < t_capture.spill_room) { t_capture.spill[t_capture.nspill++] = dev; return; }
+        /* no memory for the list: fall through and park the block now.  Nothing recorded ever runs (the capture fails), and
+         * nothing was enqueued on it since it was handed out, so it needs no event of this stream -- which is capturing. */
+        pthread_mutex_lock(&g_lock);
+        for (int i = 0; i < POOL_SLOTS; i++)
+            if (g_pool[i].ptr == dev && g_pool[i].live) {
+                g_pool[i].live = 0; g_pool[i].stamp = ++g_pool_clock; g_pool_parked += g_pool[i].bytes;
+                break;
+            }
+        pthread_mutex_unlock(&g_lock);
         return;
     }
     hipEvent_t ev = NULL;
@@ -417,6 +434,11 @@ CVS_EXPORT void cvs_pool_free(void *dev, cvs_stream_t s) {
     }
     pthread_mutex_unlock(&g_lock);
     if (!parked) release_to_driver(dev, ev);        /* over the parking limit, or a block the full table never tracked */
+}
+
+CVS_EXPORT void cvs_pool_free(void *dev, cvs_stream_t s) {
+    if (!dev || cvs_enter() != 0) return;
+    pool_free_here(dev, cvs_pick_stream(s));
 }
 
 CVS_EXPORT int cvs_mem_info(size_t *free_bytes, size_t *total_bytes) {
@@ -452,7 +474,8 @@ CVS_EXPORT void cvs_pool_trim(void) {
  * figures and pool blocks exist: nothing may allocate or synchronise while a stream is capturing).  Scratch blocks
  * the sequence takes from the pool, and the cached tables its kernels read, belong to the graph until it is destroyed.  Frame pointers and parameters are
  * baked in; the CONTENTS of the frames are whatever they hold at replay time. */
-typedef struct { hipGraph_t graph; hipGraphExec_t exec; void *blocks[GRAPH_BLOCKS]; int n; cvs_hold holds[GRAPH_BLOCKS]; int nholds; hipStream_t stream; } cvs_graph;
+typedef struct { hipGraph_t graph; hipGraphExec_t exec; void *blocks[GRAPH_BLOCKS]; int n; cvs_hold holds[GRAPH_BLOCKS]; int nholds; hipStream_t stream;
+                 int ctx; /* the context it was recorded in: its blocks belong to that context's pool, its stream and kernels to that device */ } cvs_graph;
 
 CVS_EXPORT int cvs_graph_begin(cvs_stream_t s) {
     if (cvs_enter() != 0) return -1;
@@ -477,10 +500,14 @@ CVS_EXPORT cvs_graph_t cvs_graph_end(cvs_stream_t s) {
         e = hipGraphInstantiate(&g->exec, graph, NULL, NULL, 0);
         if (e != hipSuccess) { free(g); g = NULL; }
     }
+    /* blocks past the GRAPH_BLOCKS-th (the capture has failed): not capturing any more, so back to the pool */
+    for (int i = 0; i < t_capture.nspill; i++) cvs_pool_free(t_capture.spill[i], st);
+    free(t_capture.spill);
+    t_capture.spill = NULL; t_capture.nspill = t_capture.spill_room = 0;
     if (!g) {
-        cvs_set_error("graph capture failed: %s", t_capture.overflow ? "too many scratch blocks" : hipGetErrorString(e));
+        cvs_set_error("graph capture failed: %s", t_capture.overflow ? "too many scratch blocks or cached tables (at most 64 of each per graph)" : hipGetErrorString(e));
         if (graph) hipGraphDestroy(graph);
-        for (int i = 0; i < t_capture.n; i++) cvs_pool_free(t_capture.blocks[i], st);     /* not capturing any more: back to the pool */
+        for (int i = 0; i < t_capture.n; i++) cvs_pool_free(t_capture.blocks[i], st);
         for (int i = 0; i < t_capture.nholds; i++) t_capture.holds[i].release(t_capture.holds[i].arg);
         return NULL;
     }
@@ -489,25 +516,40 @@ CVS_EXPORT cvs_graph_t cvs_graph_end(cvs_stream_t s) {
     memcpy(g->holds, t_capture.holds, sizeof(cvs_hold) * (size_t)t_capture.nholds);
     g->nholds = t_capture.nholds;
     g->stream = st;
+    g->ctx = t_ctx;
     return g;
+}
+
+/* A graph may be launched or destroyed by a thread bound to another context than the one it was recorded in: the call then
+ * runs in the graph's context (its device, its pool, the thread's own stream THERE for a NULL stream), and the calling
+ * thread is bound to its own context's device again before it returns. */
+static int enter_graph_context(const cvs_graph *g) {
+    if (cvs_enter() != 0) return -1;
+    if (g->ctx == t_ctx) return 0;
+    t_ctx = g->ctx;
+    if (hipSetDevice(g_ctx[t_ctx].device) != hipSuccess) { cvs_set_error("hipSetDevice(%d) failed", g_ctx[t_ctx].device); (void)cvs_enter(); return -1; }
+    return 0;
 }
 
 CVS_EXPORT int cvs_graph_launch(cvs_graph_t graph, cvs_stream_t s) {
     cvs_graph *g = graph;
-    if (cvs_enter() != 0 || !g) return -1;
-    CVS_HIP(hipGraphLaunch(g->exec, cvs_pick_stream(s)));
+    if (!g || enter_graph_context(g) != 0) return -1;
+    const hipError_t e = hipGraphLaunch(g->exec, cvs_pick_stream(s));
+    (void)cvs_enter();
+    if (e != hipSuccess) { cvs_set_error("hipGraphLaunch: %s", hipGetErrorString(e)); return -1; }
     return 0;
 }
 
 CVS_EXPORT void cvs_graph_destroy(cvs_graph_t graph) {
     cvs_graph *g = graph;
-    if (!g || cvs_enter() != 0) return;
-    (void)hipDeviceSynchronize();                 /* a replay may still be running */
+    if (!g || enter_graph_context(g) != 0) return;
+    (void)hipDeviceSynchronize();                 /* a replay may still be running (on the graph's device) */
     hipGraphExecDestroy(g->exec);
     hipGraphDestroy(g->graph);
-    for (int i = 0; i < g->n; i++) cvs_pool_free(g->blocks[i], g->stream);
+    for (int i = 0; i < g->n; i++) pool_free_here(g->blocks[i], g->stream);
     for (int i = 0; i < g->nholds; i++) g->holds[i].release(g->holds[i].arg);
     free(g);
+    (void)cvs_enter();
 }
 
 CVS_EXPORT cvs_event_t cvs_event_create(void) {

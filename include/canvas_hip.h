@@ -292,10 +292,26 @@ CVS_EXPORT void cvs_free(void *dev);
 /* recycled scratch for per-frame intermediates (no device sync on free, unlike hipFree); a block
  * handed to a different stream than it was last used on waits for that stream first */
 /* HIP graphs: record a sequence of device-frame calls on a stream once, replay it with one submission (worth it when
- * the sequence is launch-bound: many short kernels on small frames).  Rules: capturing thread = calling thread; only
- * `cvs_*_dev` entry points on the capturing stream in between; the same sequence must have run once before (tables,
- * pool blocks); frame pointers and parameters are baked in, frame CONTENTS are read at replay time; scratch blocks the
- * sequence took from the pool stay with the graph until cvs_graph_destroy. */
+ * the sequence is launch-bound: many short kernels on small frames).  The contract, which tests/test_graph_replay_gpu.py holds
+ * every cvs_*_dev entry and the workspace's device slot to:
+ *   - capturing thread = calling thread, one capture per thread at a time; between begin and end only `cvs_*_dev` entry points
+ *     (and video_get_frame_dev over sources whose device slots make such calls) on the capturing stream.  A call that names
+ *     another stream, or none, is not recorded: it runs at once.
+ *   - the same sequence must have run once before on the same geometry (tables, pool blocks, code objects exist: recording then
+ *     allocates nothing and waits for nothing).
+ *   - recording runs nothing.  Return codes and current windows are those of the direct call and are final when the call
+ *     returns; a call that refuses records nothing.  Frame pointers, windows and parameters are baked in (host arrays such as
+ *     taps and matrices are read while recording and may go away); frame CONTENTS are read at replay time.
+ *   - scratch blocks the sequence took from the pool, and the cached tap and byte tables its kernels read, stay with the graph
+ *     until cvs_graph_destroy: at most 64 blocks and 64 table holds per graph (a call pinned to the table kernels holds two tap
+ *     tables).  A capture that needs more fails at cvs_graph_end -- NULL, "too many scratch blocks or cached tables" -- with
+ *     every block back in the pool and every hold released; the thread can record again at once.  A table held by a graph is
+ *     never evicted: with all 8 byte-table slots, or all 128 tap-table slots, of a context held by graphs, a call that needs
+ *     another table fails with a message and writes nothing.
+ *   - cvs_graph_end returns NULL (message in cvs_last_error) and leaves the thread not capturing on every failure.
+ *   - a graph belongs to the device context it was recorded in.  cvs_graph_launch and cvs_graph_destroy may be called by a
+ *     thread bound to another context: they act in the graph's context (its device, its pool; a NULL stream is the calling
+ *     thread's own stream THERE) and leave the caller bound as it was.  cvs_graph_destroy waits for the graph's device first. */
 typedef void *cvs_graph_t;
 CVS_EXPORT int cvs_graph_begin(cvs_stream_t stream);
 CVS_EXPORT cvs_graph_t cvs_graph_end(cvs_stream_t stream);          /* NULL on failure */
