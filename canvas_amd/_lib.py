@@ -21,6 +21,7 @@ LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_T
 KEY_SHOW_MATTE = 1                                  # cvs_chroma_key.flags
 MATTE_SHOW, MATTE_MAX_CHOKE, MATTE_MAX_TAPS = 1, 16, 25    # cvs_matte.flags and its limits
 TRANSFORM_NEAREST, TRANSFORM_BILINEAR, TRANSFORM_MAX_COORD = 0, 1, 1 << 23    # cvs_transform.filter and the coordinate limit
+MAX_COORD, RESAMPLE_MAX_COORD = 1 << 30, 1 << 23        # the coordinate contract of canvas_hip.h: every entry's bound, the resamplers'
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 

@@ -68,10 +68,10 @@ static cvs_staged *bridge_find(cvs_bridge *b, const void *host) {
 int cvs_bridge_pull_window(cvs_bridge *b, void *host, const box2i *full, const box2i *window, size_t px) {
     const cvs_staged *st = b->rc == 0 ? bridge_find(b, host) : NULL;
     if (!st) return b->rc;
-    const size_t pitch = (size_t)(full->max.x - full->min.x + 1) * px;
+    const size_t pitch = (size_t)cvs_box_width(full) * px;
     const size_t at = (size_t)(window->min.y - full->min.y) * pitch + (size_t)(window->min.x - full->min.x) * px;
-    if (hipMemcpy2DAsync((char *)host + at, pitch, (const char *)st->dev + at, pitch, (size_t)(window->max.x - window->min.x + 1) * px,
-                         (size_t)(window->max.y - window->min.y + 1), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+    if (hipMemcpy2DAsync((char *)host + at, pitch, (const char *)st->dev + at, pitch, (size_t)cvs_box_width(window) * px,
+                         (size_t)cvs_box_height(window), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
         hipStreamSynchronize(b->stream) != hipSuccess)
         b->rc = -1;
     return b->rc;

@@ -13,6 +13,7 @@
 CVS_EXPORT int cvs_color_matrix_f16_dev(rgba_frame_f16 *frame, const float m[9], int pre_lut, int post_lut, cvs_stream_t s) {
     if (cvs_enter() != 0) return -1;
     CVS_REQUIRE_INSIDE(frame, frame, "cvs_color_matrix_f16_dev");
+    CVS_REQUIRE_COORDS(frame, 1, frame, "cvs_color_matrix_f16_dev", "frame");
     if (box2i_is_empty(&frame->current_window)) return 0;
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("colour matrix: current_window outside the buffer"); return -1; }
     const half *pre = cvs_lut_dev_or_null(pre_lut), *post = cvs_lut_dev_or_null(post_lut);
@@ -27,6 +28,8 @@ CVS_EXPORT int cvs_color_matrix_f16_dev(rgba_frame_f16 *frame, const float m[9],
 CVS_EXPORT int cvs_color_matrix_f16_to_dev(rgba_frame_f16 *out, const rgba_frame_f16 *in, const float m[9], int pre_lut, int post_lut, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(in, out, "cvs_color_matrix_f16_to_dev");
+    CVS_REQUIRE_COORDS(in, 1, out, "cvs_color_matrix_f16_to_dev", "in");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_color_matrix_f16_to_dev", "out");
     box2i win;
     box2i_intersect(&win, &out->full_window, &in->current_window);
     out->current_window = win;
@@ -145,6 +148,16 @@ CVS_EXPORT int cvs_chain_color_over_f16_dev(const cvs_chain_job *jobs, int njobs
                                             int pre_lut, int post_lut, cvs_stream_t stream) {
     if (cvs_enter() != 0) return -1;
     if (njobs <= 0) return 0;
+    /* before anything is launched for any job: every frame of every job inside the coordinate contract */
+    for (int i = 0; i < njobs; i++) {
+        bool refused = cvs_coords_refused("cvs_chain_color_over_f16_dev", "a job's output", &jobs[i].out->full_window, NULL, CVS_MAX_COORD);
+        for (int k = 0; !refused && k < jobs[i].nlayers && k < CVS_CHAIN_MAX_LAYERS; k++)
+            refused = cvs_coords_refused("cvs_chain_color_over_f16_dev", "a layer", &jobs[i].layers[k]->full_window, &jobs[i].layers[k]->current_window, CVS_MAX_COORD);
+        if (refused) {
+            for (int j = 0; j < njobs; j++) box2i_set_empty(&jobs[j].out->current_window);
+            return -1;
+        }
+    }
     hipStream_t s = cvs_pick_stream(stream);
     if (!m && (pre_lut != CVS_LUT_NONE || post_lut != CVS_LUT_NONE)) { cvs_set_error("chain: transfer tables need a colour matrix (m == NULL means no colour stage)"); return -1; }
     const half *pre = cvs_lut_dev_or_null(pre_lut), *post = cvs_lut_dev_or_null(post_lut);
@@ -196,6 +209,9 @@ CVS_EXPORT int cvs_mix_cross_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(a, out, "cvs_mix_cross_f16_dev");
     CVS_REQUIRE_INSIDE(b, out, "cvs_mix_cross_f16_dev");
+    CVS_REQUIRE_COORDS(a, 1, out, "cvs_mix_cross_f16_dev", "a");
+    CVS_REQUIRE_COORDS(b, 1, out, "cvs_mix_cross_f16_dev", "b");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_mix_cross_f16_dev", "out");
     hipStream_t s = cvs_pick_stream(stream);
     mix_b = clampf(mix_b, 0.0f, 1.0f);
     const cvs_chain_job job = { out, { a, b }, 2 };

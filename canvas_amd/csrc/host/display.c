@@ -93,6 +93,7 @@ static int to_bytes_dev(void *dst_dev, const rgba_frame_f16 *frame, int pre_lut,
 CVS_EXPORT int cvs_frame_to_rgba8_intent_dev(void *dst_dev, const rgba_frame_f16 *frame, int pre_lut, float rendering_intent, cvs_stream_t stream) {
     if (cvs_enter() != 0) return -1;
     if (box2i_is_empty(&frame->current_window)) return 0;
+    if (cvs_coords_refused("cvs_frame_to_rgba8_intent_dev", "frame", &frame->full_window, &frame->current_window, CVS_MAX_COORD)) return -1;
     return to_bytes_dev(dst_dev, frame, pre_lut, RAMP_INTENT, rendering_intent, CVK_DISPLAY_RGBA8, cvs_pick_stream(stream));
 }
 
@@ -101,6 +102,7 @@ CVS_EXPORT int cvs_frame_to_bytes_dev(void *dst_dev, const rgba_frame_f16 *frame
     if (cvs_enter() != 0) return -1;
     if (mode != CVS_DISPLAY_RGBA8 && mode != CVS_DISPLAY_ARGB32_PREMUL) { cvs_set_error("frame to bytes: unknown mode %d", mode); return -1; }
     if (box2i_is_empty(&frame->current_window)) return 0;
+    if (cvs_coords_refused("cvs_frame_to_bytes_dev", "frame", &frame->full_window, &frame->current_window, CVS_MAX_COORD)) return -1;
     return to_bytes_dev(dst_dev, frame, pre_lut, RAMP_GAMMA45, 0.0f, mode == CVS_DISPLAY_RGBA8 ? CVK_DISPLAY_RGBA8 : CVK_DISPLAY_ARGB32_PREMUL, cvs_pick_stream(stream));
 }
 
@@ -111,11 +113,12 @@ static int host_to_bytes(void *dst_host, const rgba_frame_f16 *frame, int pre_lu
     const box2i *w = &frame->current_window;
     if (box2i_is_empty(w)) return 0;
     if (!cvs_box_contains(&frame->full_window, w)) { cvs_set_error("frame to bytes: current window outside the buffer"); return -1; }
+    if (cvs_coords_refused("video_frame_to_bytes", "frame", &frame->full_window, w, CVS_MAX_COORD)) return -1;      /* before a byte is staged */
     hipStream_t s = cvs_pick_stream(NULL);
     /* only the rows of the current window travel: a device frame whose full window is that band of rows */
     rgba_frame_f16 band = *frame;
     band.full_window.min.y = w->min.y; band.full_window.max.y = w->max.y;
-    const size_t pitch = (size_t)(frame->full_window.max.x - frame->full_window.min.x + 1);
+    const size_t pitch = (size_t)cvs_box_width(&frame->full_window);
     const rgba_f16 *first = frame->data + (size_t)(w->min.y - frame->full_window.min.y) * pitch;
     const size_t in_bytes = cvs_box_pixels(&band.full_window) * sizeof(rgba_f16), out_bytes = cvs_box_pixels(w) * 4;
     cvs_staged din = { 0 }, dout = { 0 };

@@ -55,6 +55,7 @@ static bool dv_planes_ok(const coded_image *p) { return cvs_planes_check(p, DV_W
 /* frame and planes on the device */
 CVS_EXPORT int cvs_reconstruct_dv_dev(rgba_frame_f16 *frame, const coded_image *planar, cvs_stream_t stream) {
     if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return -1; }
+    CVS_REQUIRE_COORDS(frame, 0, frame, "cvs_reconstruct_dv_dev", "frame");
     if (!dv_planes_ok(planar)) { cvs_set_error("DV reconstruct: need three 720x480 / 180x480 planes"); box2i_set_empty(&frame->current_window); return -1; }
     box2i_set(&frame->current_window, max(0, frame->full_window.min.x), max(DV_OFF_Y, frame->full_window.min.y),
               min(DV_W - 1, frame->full_window.max.x), min(DV_H + DV_OFF_Y - 1, frame->full_window.max.y));
@@ -71,6 +72,7 @@ CVS_EXPORT int cvs_reconstruct_dv_dev(rgba_frame_f16 *frame, const coded_image *
  * encode_input_in_place: leave the frame's rows transfer-encoded, as video_subsample.c:144 does */
 CVS_EXPORT int cvs_subsample_dv_dev(coded_image *planar, rgba_frame_f16 *frame, int encode_input_in_place, cvs_stream_t stream) {
     if (cvs_enter() != 0) return -1;
+    if (cvs_coords_refused("cvs_subsample_dv_dev", "frame", &frame->full_window, &frame->current_window, CVS_MAX_COORD)) return -1;     /* the planes stay untouched */
     if (!dv_planes_ok(planar)) { cvs_set_error("DV subsample: need three 720x480 / 180x480 planes"); return -1; }
     hipStream_t s = cvs_pick_stream(stream);
     for (int p = 0; p < 3; p++) CVS_HIP(hipMemsetAsync(planar->data[p], 0, (size_t)planar->stride[p] * DV_H, s));

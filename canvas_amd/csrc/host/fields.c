@@ -20,6 +20,8 @@ static int fields_enter(const char *what, rgba_frame_f16 *out, const rgba_frame_
         cvs_set_error("%s: an input's current_window lies outside its buffer", what);
         return -1;
     }
+    if (cvs_coords_refused(what, "out", &out->full_window, NULL, CVS_MAX_COORD) || cvs_coords_refused(what, "an input", &a->full_window, &a->current_window, CVS_MAX_COORD) ||
+        cvs_coords_refused(what, "an input", &b->full_window, &b->current_window, CVS_MAX_COORD)) return -1;
     return cvs_enter();
 }
 

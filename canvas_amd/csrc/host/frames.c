@@ -21,6 +21,8 @@
 CVS_EXPORT int cvs_copy_frame_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *in, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(in, out, "cvs_copy_frame_f16_dev");
+    CVS_REQUIRE_COORDS(in, 1, out, "cvs_copy_frame_f16_dev", "in");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_copy_frame_f16_dev", "out");
     box2i inner;
     box2i_intersect(&inner, &out->full_window, &in->current_window);
     out->current_window = inner;
@@ -47,6 +49,8 @@ CVS_EXPORT int cvs_pulldown23_frames(int offset, int frame_index, int *first, in
 /* :88-104: `other` was pulled into a buffer allocated for frame->current_window; its even rows replace the frame's */
 CVS_EXPORT int cvs_weave_fields_f16_dev(rgba_frame_f16 *frame, const rgba_frame_f16 *other, cvs_stream_t s) {
     if (cvs_enter() != 0) return -1;
+    CVS_REQUIRE_COORDS(frame, 1, frame, "cvs_weave_fields_f16_dev", "frame");
+    if (cvs_coords_refused("cvs_weave_fields_f16_dev", "other", &other->full_window, &other->current_window, CVS_MAX_COORD)) { box2i_set_empty(&frame->current_window); return -1; }
     if (box2i_is_empty(&frame->current_window)) return 0;
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("cvs_weave_fields_f16_dev: current window outside the buffer"); return -1; }
     if (memcmp(&other->full_window, &frame->current_window, sizeof(box2i)) != 0) {
@@ -62,6 +66,8 @@ CVS_EXPORT int cvs_weave_fields_f16_dev(rgba_frame_f16 *frame, const rgba_frame_
 CVS_EXPORT int cvs_copy_frame_alpha_f32_dev(rgba_frame_f32 *out, const rgba_frame_f32 *in, float alpha, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(in, out, "cvs_copy_frame_alpha_f32_dev");
+    CVS_REQUIRE_COORDS(in, 1, out, "cvs_copy_frame_alpha_f32_dev", "in");
+    CVS_REQUIRE_COORDS(out, out->data == in->data, out, "cvs_copy_frame_alpha_f32_dev", "out");
     alpha = clampf(alpha, 0.0f, 1.0f);
     if (out->data == in->data && alpha == 1.0f) return 0;             /* video_mix.c:77-78 (same frame, nothing to do) */
     if (alpha == 0.0f) { box2i_set_empty(&out->current_window); return 0; }
@@ -76,6 +82,8 @@ CVS_EXPORT int cvs_copy_frame_alpha_f32_dev(rgba_frame_f32 *out, const rgba_fram
 CVS_EXPORT int cvs_frame_f16_to_f32_dev(rgba_frame_f32 *out, const rgba_frame_f16 *in, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(in, out, "cvs_frame_f16_to_f32_dev");
+    CVS_REQUIRE_COORDS(in, 1, out, "cvs_frame_f16_to_f32_dev", "in");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_frame_f16_to_f32_dev", "out");
     /* main.c:115-139: the temp frame shares the target's full window, rows of current_window are widened */
     out->current_window = in->current_window;
     if (box2i_is_empty(&in->current_window)) return 0;
@@ -87,6 +95,8 @@ CVS_EXPORT int cvs_frame_f16_to_f32_dev(rgba_frame_f32 *out, const rgba_frame_f1
 CVS_EXPORT int cvs_frame_f32_to_f16_dev(rgba_frame_f16 *out, const rgba_frame_f32 *in, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(in, out, "cvs_frame_f32_to_f16_dev");
+    CVS_REQUIRE_COORDS(in, 1, out, "cvs_frame_f32_to_f16_dev", "in");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_frame_f32_to_f16_dev", "out");
     out->current_window = in->current_window;                          /* main.c:43-71 */
     if (box2i_is_empty(&in->current_window)) return 0;
     if (!cvs_box_contains(&out->full_window, &in->current_window)) { cvs_set_error("f32->f16: source window outside target buffer"); box2i_set_empty(&out->current_window); return -1; }
@@ -130,6 +140,9 @@ CVS_EXPORT int cvs_mix_cross_f32_dev(rgba_frame_f32 *out, const rgba_frame_f32 *
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(a, out, "cvs_mix_cross_f32_dev");
     CVS_REQUIRE_INSIDE(b, out, "cvs_mix_cross_f32_dev");
+    CVS_REQUIRE_COORDS(a, 1, out, "cvs_mix_cross_f32_dev", "a");
+    CVS_REQUIRE_COORDS(b, 1, out, "cvs_mix_cross_f32_dev", "b");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_mix_cross_f32_dev", "out");
     mix_b = clampf(mix_b, 0.0f, 1.0f);
     const float mix_a = 1.0f - mix_b;
     if (box2i_is_empty(&a->current_window)) return cvs_copy_frame_alpha_f32_dev(out, b, mix_b, s);
@@ -147,6 +160,8 @@ CVS_EXPORT int cvs_mix_over_f32_dev(rgba_frame_f32 *out, const rgba_frame_f32 *b
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(b, out, "cvs_mix_over_f32_dev");
     CVS_REQUIRE_INSIDE(out, out, "cvs_mix_over_f32_dev");
+    CVS_REQUIRE_COORDS(b, 1, out, "cvs_mix_over_f32_dev", "b");
+    CVS_REQUIRE_COORDS(out, 1, out, "cvs_mix_over_f32_dev", "out");
     mix_b = clampf(mix_b, 0.0f, 1.0f);
     if (box2i_is_empty(&out->current_window)) return cvs_copy_frame_alpha_f32_dev(out, b, mix_b, s);
     if (box2i_is_empty(&b->current_window) || mix_b == 0.0f) return 0;
@@ -162,6 +177,8 @@ CVS_EXPORT int cvs_mix_over_f32_dev(rgba_frame_f32 *out, const rgba_frame_f32 *b
 CVS_EXPORT int cvs_gain_offset_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *in, float gain, float offset, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(in, out, "cvs_gain_offset_f16_dev");
+    CVS_REQUIRE_COORDS(in, 1, out, "cvs_gain_offset_f16_dev", "in");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_gain_offset_f16_dev", "out");
     box2i win;
     box2i_intersect(&win, &out->full_window, &in->current_window);    /* gl.c:584: one-input filters cover out.full ∩ in.current */
     out->current_window = win;
@@ -172,6 +189,7 @@ CVS_EXPORT int cvs_gain_offset_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16
 
 CVS_EXPORT int cvs_fill_solid_f16_dev(rgba_frame_f16 *frame, const box2i *window, const rgba_f32 *color, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return -1; }
+    CVS_REQUIRE_COORDS(frame, 0, frame, "cvs_fill_solid_f16_dev", "frame");     /* `window` is clipped, by comparisons alone: any box */
     box2i_intersect(&frame->current_window, window, &frame->full_window);
     if (box2i_is_empty(&frame->current_window)) return 0;
     /* the colour is truncated to half inside the kernel (SolidColorVideoSource.c:68-69: once per frame, same rounding) */
@@ -182,6 +200,7 @@ CVS_EXPORT int cvs_fill_solid_f16_dev(rgba_frame_f16 *frame, const box2i *window
 
 CVS_EXPORT int cvs_fill_solid_f32_dev(rgba_frame_f32 *frame, const box2i *window, const rgba_f32 *color, cvs_stream_t s) {
     if (cvs_enter() != 0) { box2i_set_empty(&frame->current_window); return -1; }
+    CVS_REQUIRE_COORDS(frame, 0, frame, "cvs_fill_solid_f32_dev", "frame");     /* `window` is clipped, by comparisons alone: any box */
     box2i_intersect(&frame->current_window, window, &frame->full_window);
     if (box2i_is_empty(&frame->current_window)) return 0;
     CVS_KERNEL(cvk_fill_f32(cvs_view(frame->data, &frame->full_window), cvs_rect(&frame->current_window), (const float *)color, cvs_pick_stream(s)));

@@ -60,16 +60,16 @@ int cvs_enter(void);
 hipStream_t cvs_pick_stream(cvs_stream_t s);
 int cvs_cus(void);
 
-static inline size_t cvs_box_pixels(const box2i *b) {
-    v2i s;
-    box2i_get_size(b, &s);
-    return (size_t)s.x * (size_t)s.y;
-}
+/* width and height in 64 bit: max - min + 1 of a box2i does not fit an int for every box (canvas_hip.h box2i_get_size does it
+ * in int, as the reference's does, and is for boxes inside the coordinate contract) */
+static inline long long cvs_box_width(const box2i *b) { return box2i_is_empty(b) ? 0 : (long long)b->max.x - b->min.x + 1; }
+static inline long long cvs_box_height(const box2i *b) { return box2i_is_empty(b) ? 0 : (long long)b->max.y - b->min.y + 1; }
+static inline size_t cvs_box_pixels(const box2i *b) { return (size_t)cvs_box_width(b) * (size_t)cvs_box_height(b); }
 
 static inline cvk_view cvs_view(void *data, const box2i *full) {
     cvk_view v;
     v.data = data;
-    v.pitch = full->max.x < full->min.x ? 0 : full->max.x - full->min.x + 1;
+    v.pitch = full->max.x < full->min.x ? 0 : (int)((long long)full->max.x - full->min.x + 1);     /* (fits: cvs_coords_refused) */
     v.fx0 = full->min.x; v.fy0 = full->min.y; v.fx1 = full->max.x; v.fy1 = full->max.y;
     return v;
 }
@@ -93,6 +93,41 @@ static inline bool cvs_box_contains(const box2i *outer, const box2i *inner) {
             box2i_set_empty(&(out_frame)->current_window);                                                 \
             return -1;                                                                                     \
         }                                                                                                  \
+    } while (0)
+
+/* The coordinate contract (canvas_hip.h, beside the frame structs; DESIGN.md "Coordinates"): kernels and launchers form
+ * y1 + 1, x + 127, y0 + seg - 1, window + halo in `int`, which is exact only while the coordinates leave headroom.  An operand
+ * outside +-lim, or a buffer whose width or height does not fit an int, is refused here, before anything is launched. */
+static inline bool cvs_box_within(const box2i *b, int lim) {
+    return box2i_is_empty(b) || (b->min.x >= -lim && b->min.y >= -lim && b->max.x <= lim && b->max.y <= lim);
+}
+/* true, with the error set, for a frame operand the contract excludes.  `cur`: NULL where the entry does not read the
+ * operand's current_window (a pure output).  Empty windows are exempt. */
+static inline bool cvs_coords_refused(const char *what, const char *operand, const box2i *full, const box2i *cur, int lim) {
+    const box2i *bad = !cvs_box_within(full, lim) ? full : (cur && !cvs_box_within(cur, lim) ? cur : NULL);
+    if (bad) {
+        cvs_set_error("%s: %s: %s (%d, %d)-(%d, %d) has a coordinate beyond +-%d%s", what, operand, bad == full ? "full_window" : "current_window",
+                      bad->min.x, bad->min.y, bad->max.x, bad->max.y, lim, lim == CVS_MAX_COORD ? " (CVS_MAX_COORD)" : ", where a float no longer holds every integer");
+        return true;
+    }
+    if (cvs_box_width(full) > 0x7fffffffLL || cvs_box_height(full) > 0x7fffffffLL) {
+        cvs_set_error("%s: %s: full_window is %lld x %lld, which no int holds", what, operand, cvs_box_width(full), cvs_box_height(full));
+        return true;
+    }
+    return false;
+}
+static inline bool cvs_point_refused(const char *what, const char *operand, v2f p, int lim) {
+    if (p.x >= -(float)lim && p.x <= (float)lim && p.y >= -(float)lim && p.y <= (float)lim) return false;
+    cvs_set_error("%s: %s: point (%g, %g) lies beyond +-%d", what, operand, p.x, p.y, lim);
+    return true;
+}
+/* a frame of either format; reads_cur: the entry reads its current_window (an input, an output worked on in place) */
+#define CVS_REQUIRE_COORDS(frame, reads_cur, out_frame, what, operand)                                                         \
+    do {                                                                                                                       \
+        if (cvs_coords_refused(what, operand, &(frame)->full_window, (reads_cur) ? &(frame)->current_window : NULL, CVS_MAX_COORD)) { \
+            box2i_set_empty(&(out_frame)->current_window);                                                                     \
+            return -1;                                                                                                         \
+        }                                                                                                                      \
     } while (0)
 
 /* ---- staging of one flat host array (halfconv.c, display.c; the bridge below is built on it): H2D -> kernels -> D2H */
@@ -140,9 +175,15 @@ int cvs_bridge_pull_window(cvs_bridge *b, void *host, const box2i *full, const b
 int cvs_bridge_close(cvs_bridge *b, void *out_host);
 
 static inline size_t cvs_frame_bytes(const box2i *full, size_t px) { return cvs_box_pixels(full) * px; }
-/* dst = the device twin of host frame *src (either format): the same windows, the data pointer from the bridge */
+/* dst = the device twin of host frame *src (either format): the same windows, the data pointer from the bridge.  A buffer
+ * outside the coordinate contract fails the bridge before a byte is staged for it (the `_dev` twin would refuse it, and names
+ * itself when a current_window is what breaks the contract). */
 #define CVS_BRIDGE_FRAME(b, dst, src, flags)                                                                                  \
-    do { (dst) = *(src); (dst).data = cvs_bridge_frame(b, (src)->data, cvs_frame_bytes(&(src)->full_window, sizeof *(src)->data), flags); } while (0)
+    do {                                                                                                                      \
+        (dst) = *(src);                                                                                                       \
+        if ((b)->rc == 0 && cvs_coords_refused("host frame", #src, &(src)->full_window, NULL, CVS_MAX_COORD)) (b)->rc = -1;   \
+        (dst).data = cvs_bridge_frame(b, (src)->data, cvs_frame_bytes(&(src)->full_window, sizeof *(src)->data), flags);      \
+    } while (0)
 /* fn(args..., the bridge's stream) unless an earlier step failed */
 #define CVS_BRIDGE_CALL(b, fn, ...) do { if ((b)->rc == 0) (b)->rc = fn(__VA_ARGS__, (b)->stream); } while (0)
 

@@ -18,6 +18,7 @@ static int chroma_key(void *tdata, const box2i *tfull, box2i *tcur, const void *
                       const cvs_chroma_key *key, int half, cvs_stream_t stream, const char *what) {
     box2i_set_empty(tcur);
     if (!cvs_box_contains(sfull, scur)) { cvs_set_error("%s: the input's current_window lies outside its buffer", what); return -1; }
+    if (cvs_coords_refused(what, "source", sfull, scur, CVS_MAX_COORD) || cvs_coords_refused(what, "target", tfull, NULL, CVS_MAX_COORD)) return -1;
     if (!isfinite(key->key[0]) || !isfinite(key->key[1]) || !isfinite(key->key[2])) { cvs_set_error("%s: the key colour is not finite", what); return -1; }
     if (!width_ok(key->tolerance) || !width_ok(key->softness) || !width_ok(key->spill_range)) {
         cvs_set_error("%s: tolerance %g, softness %g and spill_range %g must be finite and not negative", what, key->tolerance, key->softness, key->spill_range);

@@ -25,6 +25,7 @@ static int matte_refine(void *tdata, const box2i *tfull, box2i *tcur, const void
                         const cvs_matte *m, int half, cvs_stream_t stream, const char *what) {
     box2i_set_empty(tcur);
     if (!cvs_box_contains(sfull, scur)) { cvs_set_error("%s: the input's current_window lies outside its buffer", what); return -1; }
+    if (cvs_coords_refused(what, "source", sfull, scur, CVS_MAX_COORD) || cvs_coords_refused(what, "target", tfull, NULL, CVS_MAX_COORD)) return -1;
     if (m->choke > CVS_MATTE_MAX_CHOKE || m->choke < -CVS_MATTE_MAX_CHOKE) { cvs_set_error("%s: choke %d is beyond +-%d", what, m->choke, CVS_MATTE_MAX_CHOKE); return -1; }
     if (m->ntaps < 0 || m->ntaps > CVS_MATTE_MAX_TAPS || (m->ntaps > 0 && !(m->ntaps & 1))) {
         cvs_set_error("%s: the feather takes 0 or an odd count of up to %d taps, not %d", what, CVS_MATTE_MAX_TAPS, m->ntaps);

@@ -28,6 +28,7 @@ CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16
         return -1;
     }
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("MPEG-2 subsample: current window outside the buffer"); return -1; }
+    if (cvs_coords_refused("cvs_subsample_mpeg2_dev", "frame", &frame->full_window, &frame->current_window, CVS_MAX_COORD)) return -1;
     /* pixels outside the current window (and outside the raster) count as black: the kernel reads inside w only */
     box2i w;
     box2i_set(&w, max(0, frame->current_window.min.x), max(0, frame->current_window.min.y),
@@ -52,6 +53,7 @@ CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame) {
     coded_image dev;
     if (cvs_bridge_open(&br) != 0 || !frame) return NULL;
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("MPEG-2 subsample: current window outside the buffer"); return NULL; }
+    if (cvs_coords_refused("video_subsample_mpeg2", "frame", &frame->full_window, &frame->current_window, CVS_MAX_COORD)) return NULL;
     coded_image *out = coded_image_alloc(strides, lines, 3);
     if (!out) return NULL;
     /* a frame without pixels is not read: one byte stands in for its buffer */
@@ -79,6 +81,7 @@ CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_imag
     if (!frame) { cvs_set_error("MPEG-2 reconstruct: need a frame"); return -1; }
     box2i_set_empty(&frame->current_window);
     if (cvs_enter() != 0) return -1;
+    if (cvs_coords_refused("cvs_reconstruct_mpeg2_dev", "frame", &frame->full_window, NULL, CVS_MAX_COORD)) return -1;
     const bool progressive = (flags & CVS_YCC_PROGRESSIVE) != 0;
     if (flags & ~(CVS_YCC_PROGRESSIVE | CVS_YCC_REC709)) { cvs_set_error("MPEG-2 reconstruct: unknown flags 0x%x", (unsigned)flags); return -1; }
     if (!recon_size_ok(width, height, progressive)) {

@@ -70,13 +70,18 @@ static any_frame any_of(const frame_ref *f, int half) {
 
 /* What a single-frame entry checks first, with its frames as frame_of() reads them into *t, *src: a device for the call,
  * and a source window inside its own buffer (else a kernel would read past it).  On refusal the target's window is
- * emptied; `what` names the entry point. */
-static bool entry_refused(void *target, const void *source, int half, const char *what, frame_ref *t, frame_ref *src) {
+ * emptied; `what` names the entry point.  `lim`: the coordinate bound of the entry's family (CVS_MAX_COORD; the resamplers,
+ * which form positions in float: CVS_RESAMPLE_MAX_COORD). */
+static bool entry_refused(void *target, const void *source, int half, const char *what, frame_ref *t, frame_ref *src, int lim) {
     *t = frame_of(target, half);
     *src = frame_of(source, half);
     if (cvs_enter() != 0) { box2i_set_empty(t->cur); return true; }
     if (!cvs_box_contains(src->full, src->cur)) {
         cvs_set_error("%s: the input's current_window lies outside its buffer", what);
+        box2i_set_empty(t->cur);
+        return true;
+    }
+    if (cvs_coords_refused(what, "source", src->full, src->cur, lim) || cvs_coords_refused(what, "target", t->full, NULL, lim)) {
         box2i_set_empty(t->cur);
         return true;
     }
@@ -90,7 +95,7 @@ static void batch_empty_from(const void *targets, int from, int count, int half)
 /* What `count` single calls would refuse, a batch entry refuses before anything is launched: null arrays or frames; a
  * source window outside its buffer (it would send a kernel's rows out of bounds) or no device, with every target's window
  * emptied. */
-static bool batch_refused(const void *targets, const void *sources, int count, int half, const char *what) {
+static bool batch_refused(const void *targets, const void *sources, int count, int half, const char *what, int lim) {
     if (!targets || !sources) { cvs_set_error("%s: bad arguments", what); return true; }
     for (int i = 0; i < count; i++)
         if (!frame_at(targets, i, half).frame || !frame_at(sources, i, half).frame) {
@@ -101,6 +106,10 @@ static bool batch_refused(const void *targets, const void *sources, int count, i
         const frame_ref src = frame_at(sources, i, half);
         if (!cvs_box_contains(src.full, src.cur)) {
             cvs_set_error("%s: the input's current_window lies outside its buffer (frame %d)", what, i);
+            batch_empty_from(targets, 0, count, half);
+            return true;
+        }
+        if (cvs_coords_refused(what, "a source", src.full, src.cur, lim) || cvs_coords_refused(what, "a target", frame_at(targets, i, half).full, NULL, lim)) {
             batch_empty_from(targets, 0, count, half);
             return true;
         }
@@ -345,7 +354,11 @@ static int scale_core(any_frame *target, v2f tp, const any_frame *source, v2f sp
  * half-native source, without the widened copy of the input and the f32 copy of the output ever existing. */
 static int scale_frame(void *target, v2f tp, const void *source, v2f sp, v2f fac, int half, cvs_stream_t stream, const char *what) {
     frame_ref t, src;
-    if (entry_refused(target, source, half, what, &t, &src)) return -1;
+    if (entry_refused(target, source, half, what, &t, &src, CVS_RESAMPLE_MAX_COORD)) return -1;
+    if (cvs_point_refused(what, "the target point", tp, CVS_RESAMPLE_MAX_COORD) || cvs_point_refused(what, "the source point", sp, CVS_RESAMPLE_MAX_COORD)) {
+        box2i_set_empty(t.cur);
+        return -1;
+    }
     hipStream_t s = cvs_pick_stream(stream);
     if (fac.x == 1.0f && tp.x == sp.x && fac.y == 1.0f && tp.y == sp.y)
         return half ? cvs_copy_frame_f16_dev(target, source, s) : cvs_copy_frame_alpha_f32_dev(target, source, 1.0f, s);
@@ -373,7 +386,11 @@ CVS_EXPORT int cvs_scale_bilinear_f16_dev(rgba_frame_f16 *target, v2f tp, const 
 static int scale_batch_frames(const void *targets, v2f tp, const void *sources, v2f sp, v2f fac, int count, int half,
                               cvs_stream_t stream, const char *what) {
     if (count <= 0) return 0;
-    if (batch_refused(targets, sources, count, half, what)) return -1;
+    if (batch_refused(targets, sources, count, half, what, CVS_RESAMPLE_MAX_COORD)) return -1;
+    if (cvs_point_refused(what, "the target point", tp, CVS_RESAMPLE_MAX_COORD) || cvs_point_refused(what, "the source point", sp, CVS_RESAMPLE_MAX_COORD)) {
+        batch_empty_from(targets, 0, count, half);
+        return -1;
+    }
     hipStream_t s = cvs_pick_stream(stream);
     const size_t px = half ? sizeof(rgba_f16) : sizeof(rgba_f32);
     int rc = 0, done = 0;
@@ -435,6 +452,13 @@ CVS_EXPORT void video_scale_bilinear_f32_pull(rgba_frame_f32 *target, v2f tp, vi
     if (fac.x == 0.0f || fac.y == 0.0f) { box2i_set_empty(&target->current_window); return; }   /* video_scale.c:290-293 */
     if (fac.x == 1.0f && fac.y == 1.0f && tp.x == sp.x && tp.y == sp.y) { video_get_frame_f32(source, frame, target); return; }
     const box2i *tf = &target->full_window;
+    /* before the pull rectangle is formed: (int) of a float beyond 2^31 is undefined, and the scaler below would refuse these */
+    if (cvs_coords_refused("video_scale_bilinear_f32_pull", "target", tf, NULL, CVS_RESAMPLE_MAX_COORD) ||
+        cvs_point_refused("video_scale_bilinear_f32_pull", "the target point", tp, CVS_RESAMPLE_MAX_COORD) ||
+        cvs_point_refused("video_scale_bilinear_f32_pull", "the source point", sp, CVS_RESAMPLE_MAX_COORD)) {
+        box2i_set_empty(&target->current_window);
+        return;
+    }
     rgba_frame_f32 tmp;
     box2i_set(&tmp.full_window,
               (int)(sp.x - (tp.x - tf->min.x) / fac.x) - 1, (int)(sp.y - (tp.y - tf->min.y) / fac.y) - 1,
@@ -627,7 +651,7 @@ static int lanczos_fused(const any_frame *t, const any_frame *src, float fx, flo
  * computes (widen, framework.h f16->f32 path; both passes in f32; truncate on the way out), in one launch. */
 static int fir_blur(void *target, const void *source, const float *taps, int ntaps, int half, cvs_stream_t stream, const char *what) {
     frame_ref t, src;
-    if (entry_refused(target, source, half, what, &t, &src)) return -1;
+    if (entry_refused(target, source, half, what, &t, &src, CVS_MAX_COORD)) return -1;
     if (ntaps < 1 || !taps) { cvs_set_error("blur: need at least one tap"); box2i_set_empty(t.cur); return -1; }
     hipStream_t s = cvs_pick_stream(stream);
     box2i win;
@@ -655,7 +679,7 @@ CVS_EXPORT int cvs_fir_blur_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16
 static int unsharp_mask(void *target, const void *source, const float *taps, int ntaps, float amount, float threshold, int half,
                         cvs_stream_t stream, const char *what) {
     frame_ref t, src;
-    if (entry_refused(target, source, half, what, &t, &src)) return -1;
+    if (entry_refused(target, source, half, what, &t, &src, CVS_MAX_COORD)) return -1;
     if (ntaps < 1 || !taps) { cvs_set_error("unsharp mask: need at least one tap"); box2i_set_empty(t.cur); return -1; }
     hipStream_t s = cvs_pick_stream(stream);
     box2i win;
@@ -712,6 +736,9 @@ CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *
                                      const rgba_frame_f16 *const *overlays, int noverlays, cvs_stream_t stream) {
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(source, out, "cvs_blur_over_f16_dev");
+    CVS_REQUIRE_COORDS(source, 1, out, "cvs_blur_over_f16_dev", "source");
+    CVS_REQUIRE_COORDS(out, 0, out, "cvs_blur_over_f16_dev", "out");
+    for (int l = 0; l < noverlays && overlays; l++) CVS_REQUIRE_COORDS(overlays[l], 1, out, "cvs_blur_over_f16_dev", "an overlay");
     if (ntaps < 1 || !taps || noverlays < 0 || (noverlays > 0 && !overlays)) { cvs_set_error("blur+over: bad arguments"); box2i_set_empty(&out->current_window); return -1; }
     if (noverlays == 0) return cvs_fir_blur_f16_dev(out, source, taps, ntaps, stream);       /* a stack of one: the blur node pulled as f16 */
     hipStream_t s = cvs_pick_stream(stream);
@@ -757,7 +784,7 @@ CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *
  * loads and the truncate on its stores: 8 B read per source pixel + 8 B written per target pixel, no f32 frame anywhere. */
 static int resample_lanczos(void *target, const void *source, float fx, float fy, int ksize, int half, cvs_stream_t stream, const char *what) {
     frame_ref t, src;
-    if (entry_refused(target, source, half, what, &t, &src)) return -1;
+    if (entry_refused(target, source, half, what, &t, &src, CVS_RESAMPLE_MAX_COORD)) return -1;
     if (!(fx > 0.0f) || !(fy > 0.0f) || ksize < 1 || box2i_is_empty(src.cur) || box2i_is_empty(t.full)) {
         box2i_set_empty(t.cur);
         return 0;
@@ -784,6 +811,11 @@ CVS_EXPORT int cvs_blur_lanczos_f16_dev(rgba_frame_f16 *target, const rgba_frame
                                         float fx, float fy, int ksize, cvs_stream_t stream) {
     if (cvs_enter() != 0) { box2i_set_empty(&target->current_window); return -1; }
     CVS_REQUIRE_INSIDE(source, target, "cvs_blur_lanczos_f16_dev");
+    if (cvs_coords_refused("cvs_blur_lanczos_f16_dev", "source", &source->full_window, &source->current_window, CVS_RESAMPLE_MAX_COORD) ||
+        cvs_coords_refused("cvs_blur_lanczos_f16_dev", "target", &target->full_window, NULL, CVS_RESAMPLE_MAX_COORD)) {
+        box2i_set_empty(&target->current_window);
+        return -1;
+    }
     if (ntaps < 1 || !taps || !(fx > 0.0f) || !(fy > 0.0f) || ksize < 1) { cvs_set_error("blur+lanczos: bad arguments"); box2i_set_empty(&target->current_window); return -1; }
     if (box2i_is_empty(&source->current_window) || box2i_is_empty(&target->full_window)) { box2i_set_empty(&target->current_window); return 0; }
     hipStream_t s = cvs_pick_stream(stream);
@@ -823,7 +855,9 @@ CVS_EXPORT int cvs_blur_over_f16_batch_dev(rgba_frame_f16 *const *outs, const rg
     for (int i = 0; i < count; i++)
         for (int l = 0; l < noverlays; l++)
             if (!overlays[(size_t)i * noverlays + l]) { cvs_set_error("%s: layer %d of frame %d is a null pointer", what, l, i); return -1; }
-    if (batch_refused(outs, sources, count, 1, what)) return -1;
+    if (batch_refused(outs, sources, count, 1, what, CVS_MAX_COORD)) return -1;
+    for (int i = 0; i < count * noverlays; i++)
+        if (cvs_coords_refused(what, "an overlay", &overlays[i]->full_window, &overlays[i]->current_window, CVS_MAX_COORD)) { batch_empty_from(outs, 0, count, 1); return -1; }
     hipStream_t s = cvs_pick_stream(stream);
     const box2i *full = &outs[0]->full_window;
     bool uniform = count > 1 && noverlays >= 1 && noverlays <= CVK_BLUR_MAX_OVER && !box2i_is_empty(full) && blur_has_fast_kernel(taps, ntaps) && (ntaps & 1);
@@ -859,7 +893,7 @@ CVS_EXPORT int cvs_blur_lanczos_f16_batch_dev(rgba_frame_f16 *const *targets, co
     const char *what = "cvs_blur_lanczos_f16_batch_dev";
     if (count <= 0) return 0;
     if (ntaps < 1 || !taps || !(fx > 0.0f) || !(fy > 0.0f) || ksize < 1) { cvs_set_error("%s: bad arguments", what); return -1; }
-    if (batch_refused(targets, sources, count, 1, what)) return -1;
+    if (batch_refused(targets, sources, count, 1, what, CVS_RESAMPLE_MAX_COORD)) return -1;
     hipStream_t s = cvs_pick_stream(stream);
     int rc = 0, done = 0;
     const box2i *tf = &targets[0]->full_window, *sw = &sources[0]->current_window;

@@ -166,6 +166,7 @@ static int transform(void *tdata, const box2i *tfull, box2i *tcur, const void *s
         cvs_set_error("%s: a window coordinate lies beyond +-%d, where a float no longer holds every integer", what, CVS_TRANSFORM_MAX_COORD);
         return -1;
     }
+    if (cvs_coords_refused(what, "source", sfull, scur, CVS_MAX_COORD) || cvs_coords_refused(what, "target", tfull, NULL, CVS_MAX_COORD)) return -1;
     if (tdata == sdata) { cvs_set_error("%s: the target is the source's buffer: the operation is not in place", what); return -1; }
     if (cvs_enter() != 0) return -1;
     if (box2i_is_empty(scur) || box2i_is_empty(tfull)) return 0;

@@ -68,7 +68,22 @@ typedef struct { float r, g, b, a; } rgba_f32; /* 16 bytes */
  *     stride * line_count bytes of a plane, the current window's pixel count * 4 bytes of a byte target.  What lies around a
  *     frame may be another frame.
  *   - an address below the pixel's alignment (a half frame at 2 modulo 8, a float frame at 4 modulo 16) is outside the
- *     contract. */
+ *     contract.
+ *
+ * Where a frame may lie on the canvas (tests/test_far_windows_gpu.py holds every windowed cvs_*_dev entry to it on frames moved
+ * up to the bound; DESIGN.md "Coordinates" has the audit behind the value):
+ *   - every coordinate of a non-empty full_window, and of a non-empty current_window the entry reads, lies within
+ *     +-CVS_MAX_COORD; so does every coordinate of an explicit window an entry does not merely clip (none today: the window of
+ *     cvs_fill_solid_* is clipped to the frame by comparisons alone and may be INT_MIN..INT_MAX, "everywhere") and every v2f point.  A
+ *     buffer's width and height are computed in 64 bit and must fit an int.  Empty windows are exempt, whatever they hold.
+ *   - an entry handed anything else returns -1 with cvs_last_error() naming the entry and the operand, every output's
+ *     current_window empty and nothing launched; the video_* entries on host frames refuse the same before they stage a byte.
+ *   - inside the bound every `int` a kernel forms from a coordinate -- plus a halo, a tile, a segment, a lane's overshoot -- is
+ *     exact: the bound leaves 2^30 - 1 of headroom and the largest such sum adds a few thousand.
+ *   - the entries that form positions in `float`, as the reference's v2f interface does, hold a tighter bound of their own,
+ *     inside which a float holds every integer: CVS_TRANSFORM_MAX_COORD for cvs_transform_*, CVS_RESAMPLE_MAX_COORD for the
+ *     bilinear scaler and the Lanczos resamplers (their windows; the points they are handed lie within it as well). */
+enum { CVS_MAX_COORD = 1 << 30, CVS_RESAMPLE_MAX_COORD = 1 << 23 };
 typedef struct { rgba_f16 *data; box2i full_window; box2i current_window; } rgba_frame_f16;
 typedef struct { rgba_f32 *data; box2i full_window; box2i current_window; } rgba_frame_f32;
 

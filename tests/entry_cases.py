@@ -69,6 +69,19 @@ class Factory:
     def aligned16(self, *frames):
         return all((f.ptr & 15) == 0 for f in frames)
 
+    # explicit geometry: every window, point and transform a case hands its entry beside the frames goes through these, so
+    # that a factory which moves the frames (Shifted, below) can move it with them
+    def box(self, x0, y0, x1, y1):
+        return box2i.of(x0, y0, x1, y1)
+
+    def point(self, x, y, source=False):
+        """A v2f in the target's coordinates, or (source=True) in the source's."""
+        return v2f(x, y)
+
+    def matrix(self, m):
+        """The six coefficients of a cvs_transform: target coordinates -> source coordinates."""
+        return tuple(m)
+
 
 class Twin(Factory):
     """Every object in an allocation of its own."""
@@ -210,7 +223,7 @@ def solid_fills(cvs):
         for half in (True, False):
             def case(fac, full=full, win=win, half=half):
                 f = fac.frame(blank(half, full), out=True)
-                b = box2i.of(*win)
+                b = fac.box(*win)
                 entry = cvs.cvs_fill_solid_f16_dev if half else cvs.cvs_fill_solid_f32_dev
                 return entry(f.ref(), C.byref(b), C.byref(color), fac.stream)
             cases.append(("fill %s %r" % ("f16" if half else "f32", (full, win)), case))
@@ -455,9 +468,8 @@ def transform(cvs, half, tw):
         sfull = (3, 1, tw - 6, th - 2)                                  # smaller than the target, window = whole buffer
         for name, m in _transforms(tw, th, sfull):
             for filt in (_lib.TRANSFORM_NEAREST, _lib.TRANSFORM_BILINEAR):
-                t = _lib.transform(m, filt)
-
-                def case(fac, tfull=tfull, sfull=sfull, t=t):
+                def case(fac, tfull=tfull, sfull=sfull, m=m, filt=filt):
+                    t = _lib.transform(fac.matrix(m), filt)
                     rng = np.random.default_rng(900 + tw + th)
                     src = fac.frame(px(rng, half, sfull))
                     out = fac.frame(blank(half, tfull), out=True, cmp="f16" if half else "f32")
@@ -648,7 +660,7 @@ def scale_bilinear(cvs, half, fac_, tsize, pin, after=None):
         src = fac.frame(px(np.random.default_rng(1400), half, sfull))
         out = fac.frame(blank(half, tfull), out=True, cmp="f16" if half else "f32")
         entry = cvs.cvs_scale_bilinear_f16_dev if half else cvs.cvs_scale_bilinear_f32_dev
-        rc = entry(out.ref(), v2f(0, 0), src.ref(), v2f(0, 0), v2f(*fac_), fac.stream)
+        rc = entry(out.ref(), fac.point(0, 0), src.ref(), fac.point(0, 0, source=True), v2f(*fac_), fac.stream)
         if after is not None:
             after(fac, out)
         return rc
@@ -658,7 +670,7 @@ def scale_bilinear(cvs, half, fac_, tsize, pin, after=None):
         srcs = [fac.frame(px(rng, half, sfull), name="source %d" % k) for k in range(3)]
         outs = [fac.frame(blank(half, tfull), out=True, cmp="f16" if half else "f32", name="target %d" % k) for k in range(3)]
         entry = cvs.cvs_scale_bilinear_f16_batch_dev if half else cvs.cvs_scale_bilinear_f32_batch_dev
-        return entry(_table(outs, cls), v2f(0, 0), _table(srcs, cls), v2f(0, 0), v2f(*fac_), 3, fac.stream)
+        return entry(_table(outs, cls), fac.point(0, 0), _table(srcs, cls), fac.point(0, 0, source=True), v2f(*fac_), 3, fac.stream)
     return [("scale %s x%r -> %r pinned %r" % ("f16" if half else "f32", fac_, tsize, pin), single),
             ("scale batch %s x%r -> %r pinned %r" % ("f16" if half else "f32", fac_, tsize, pin), batch)]
 
@@ -884,3 +896,188 @@ def _groups():
 
 
 GROUPS = _groups()
+
+
+# ------------------------------------------------------------------ far from the origin (DESIGN.md "Coordinates")
+
+MAX_COORD, RESAMPLE_MAX_COORD = _lib.MAX_COORD, _lib.RESAMPLE_MAX_COORD
+INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def move_box(b, d):
+    """(x0, y0, x1, y1) translated by d = (dx, dy); an empty box stays what it is (only emptiness is contractual)."""
+    if b[2] < b[0] or b[3] < b[1]:
+        return tuple(b)
+    return tuple(min(max(v + d[k & 1], INT_MIN), INT_MAX) for k, v in enumerate(b))
+
+
+class Shifted(Factory):
+    """Another factory's operands, moved: every frame's full_window and current_window translated by `offset` -- inputs by
+    `source_offset` where a class moves the source by another amount than the target (a resampler at factor f reads source
+    column t / f) -- and every explicit box, point and transform with them.  Pixels, coded planes and flat arrays are handed
+    on as they are.  The objects are the wrapped factory's (collect them there); windows_back() reports every frame's window
+    translated back, to compare with an unmoved run's directly.  `hosts` keeps what each frame() handed on (None for a
+    buffer) and `matrices` what matrix() returned, for expectations computed at the far arguments."""
+
+    def __init__(self, inner, offset, source_offset=None):
+        Factory.__init__(self, inner.cvs, inner.stream)
+        self.inner, self.offset = inner, tuple(offset)
+        self.source_offset = self.offset if source_offset is None else tuple(source_offset)
+        self.objects = inner.objects
+        self.moves, self.hosts, self.matrices = [], [], []
+
+    def frame(self, host, out=False, **kw):
+        d = self.offset if out else self.source_offset
+        moved = HostFrame(move_box(host.full_window.tuple(), d), host.dtype, host.array, move_box(host.current_window.tuple(), d))
+        self.moves.append(d)
+        self.hosts.append(moved)
+        return self.inner.frame(moved, out=out, **kw)
+
+    def buffer(self, data, cls, **kw):
+        self.moves.append(None)
+        self.hosts.append(None)
+        return self.inner.buffer(data, cls, **kw)
+
+    def box(self, x0, y0, x1, y1):
+        return box2i.of(*move_box((x0, y0, x1, y1), self.offset))
+
+    def point(self, x, y, source=False):
+        d = self.source_offset if source else self.offset
+        return v2f(x + d[0], y + d[1])
+
+    def matrix(self, m):
+        """source = M target + c  ->  source + Ds = M (target + Dt) + (c - M Dt + Ds)"""
+        (dx, dy), (sx, sy) = self.offset, self.source_offset
+        far = (m[0], m[1], m[2] - (m[0] * dx + m[1] * dy) + sx, m[3], m[4], m[5] - (m[3] * dx + m[4] * dy) + sy)
+        self.matrices.append(far)
+        return far
+
+    def windows_back(self):
+        out = []
+        for o, d in zip(self.objects, self.moves):
+            w = o.frame.current_window if o.frame is not None else None
+            out.append(None if w is None else box2i.of(*move_box(w.tuple(), (-d[0], -d[1]))))
+        return out
+
+
+# Every group of GROUPS in exactly one class, by the part of its id before '[':
+#   equivariant  the far result is the origin result, byte for byte
+#   modelled     the far result is the model's at the same far arguments (float positions: the bits differ from the origin's)
+#   anchored     coded planes whose raster sits at the origin: a frame far outside it gives black planes / an untouched frame
+#   unwindowed   flat arrays: nothing to move
+# with the rule its offsets follow: `even_dy` (row parity is that of the absolute coordinate), `limit` (the bound of the
+# entry's family), `source_scale` k (the source moves by k times the target's offset: Lanczos at factor 1 / k), `zero_dx`
+# (nothing moves along x), `diagonal` (dx == dy).
+_ANY = dict(even_dy=False, limit=MAX_COORD, source_scale=1, zero_dx=False, diagonal=False)
+# video_mix.c:137,265 picks its `left` frame by comparing one window's min.x with the other's min.Y (frames.c plan_mix keeps
+# that): what the mixers compute is unchanged only by an offset with dx == dy.  So for everything that reaches them with
+# ragged windows: the chain and blur + over node by node, the crossfade of halfs outside its fused form, the workspace stack.
+_DIAG = dict(_ANY, diagonal=True)
+_EVEN = dict(_ANY, even_dy=True)
+_FLOAT = dict(_ANY, limit=RESAMPLE_MAX_COORD)
+FAR_CLASSES = {
+    "copies_and_conversions": ("equivariant", _ANY), "attenuate_in_place": ("equivariant", _ANY), "solid_fills": ("equivariant", _ANY),
+    "colour_matrix": ("equivariant", _ANY), "mixers_f32": ("equivariant", _DIAG), "mix_cross_f16": ("equivariant", _DIAG),
+    "chain": ("equivariant", _ANY), "chain_batches": ("equivariant", _DIAG), "chroma_key": ("equivariant", _ANY),
+    "matte": ("equivariant", _ANY), "blur_and_unsharp": ("equivariant", _ANY), "blur_over": ("equivariant", _ANY),
+    "blur_over_forms": ("equivariant", _DIAG), "display_bytes": ("equivariant", _ANY), "workspace_stack": ("equivariant", _DIAG),
+    # the weave reproduces the reference's row address, which counts the second field's columns from x = 0 and not from the
+    # window's first column (kernels/frame_ops.hip k_weave16): what it computes depends on the absolute x, so only y moves
+    "weave_fields": ("equivariant", dict(_EVEN, zero_dx=True)), "field_conversions": ("equivariant", _EVEN),
+    # positions formed in float (the reference's v2f interface; plan_lanczos: (float)t / factor): equivariant where every
+    # position is exact -- factors 0.5 and 2.0 inside +-RESAMPLE_MAX_COORD -- and modelled at the other factors (below)
+    "scale_bilinear": ("equivariant", _FLOAT), "lanczos_resample": ("equivariant", dict(_FLOAT, source_scale=2)),
+    "blur_lanczos": ("equivariant", dict(_FLOAT, source_scale=2)), "config3_pipeline": ("equivariant", dict(_FLOAT, source_scale=2)),
+    "transform": ("modelled", dict(_ANY, limit=_lib.TRANSFORM_MAX_COORD)),
+    "dv": ("anchored", None), "mpeg2": ("anchored", None),
+    "flat_arrays": ("unwindowed", None),
+}
+# Cases of the resampler groups whose factors are no power of two: tap positions q + smin round differently at q + (smin + D),
+# so the bits are the oracle's at the far arguments, not the origin's.  The bilinear scaler at 0.5 as well: video_scale.c:257-277
+# derives the intermediate frame's window with (int)(sp - d * fac), which truncates towards zero -- a half-integer rounds up
+# below zero and down above it, so the window reported changes with the sign of the coordinates.
+# (group prefix, text in the case's name, the factors of a resampler that takes no points -- its far source must be lined up
+# with its far target, lined_up() -- or None for the scaler, whose points move with the frames)
+MODELLED_CASES = [("scale_bilinear", "x(0.5, 0.5)", None), ("scale_bilinear", "x(1.5, 1.5)", None), ("scale_bilinear", "x(0.75, 1.5)", None),
+                  ("scale_bilinear", "x(0.4, 0.35)", None),
+                  ("lanczos_resample", "-> (52, 14)", (0.4, 0.35)), ("lanczos_resample", "-> (128, 30)", (2.0, 1.5)),
+                  ("blur_lanczos", "-> (52, 14)", (0.4, 0.35)),
+                  ("config3_pipeline", "-> (128, 54)", (2.0, 1.5)), ("config3_pipeline", "-> (20, 40)", (0.1, 1.0))]
+# Every modelled case is run far (tests/test_far_windows_gpu.py; the expectations at the same offsets without a GPU:
+# tests/test_far_windows_cpu.py): the transform against tests/transform_model.py, these resampler cases in every form -- f32
+# and f16, single and batch -- against the oracle, and the field conversions and the weave, equivariant under an even dy, once
+# more at an odd dy (odd_dy_offsets), which swaps the fields, against tests/fields_model.py and the oracle.
+
+
+def _modelled(gid, what):
+    prefix = gid.split("[")[0]
+    return [m for m in MODELLED_CASES if m[0] == prefix and m[1] in what]
+
+
+def far_class(gid, what):
+    """(class, rule) of case `what` of group `gid`."""
+    prefix = gid.split("[")[0]
+    cls, rule = FAR_CLASSES[prefix]
+    if _modelled(gid, what):
+        return "modelled", rule
+    return cls, rule
+
+
+def far_offsets(rule, boxes):
+    """[(name, target offset, source offset)] for a case whose operands' full windows at the origin are `boxes`, one
+    (is_output, (x0, y0, x1, y1)) per frame: across the 16-bit lines, past a float's integers, and onto the two corners of
+    the rule's bound.  An input moves by source_scale times the target's offset."""
+    k, lim, even = rule["source_scale"], rule["limit"], rule["even_dy"]
+    named = [("across +2^15", (2 ** 15 + 1, -2 ** 15)), ("across -2^16", (-2 ** 16 - 1, 2 ** 16))]
+    if lim > 2 ** 25:
+        named.append(("past 2^24", (2 ** 24 + 1, -2 ** 24 - 2)))
+    if not even:
+        named.append(("odd dy", (-2 ** 16 - 2, 2 ** 15 + 1)))
+    scale = lambda is_out: 1 if is_out else k
+    top = [min((lim - b[2 + a]) // scale(o) for o, b in boxes) for a in (0, 1)]
+    bottom = [max(-((lim + b[a]) // scale(o)) for o, b in boxes) for a in (0, 1)]
+    if even:
+        top[1] -= top[1] & 1
+        bottom[1] += bottom[1] & 1
+    named += [("top corner", tuple(top)), ("bottom corner", tuple(bottom))]
+    if rule["zero_dx"]:
+        named = [(name, (0, d[1])) for name, d in named]
+    if rule["diagonal"]:              # on a corner: the axis that reaches the bound first
+        named = [(name, (min(d, key=abs),) * 2 if "corner" in name else (d[0], d[0])) for name, d in named]
+    out = []
+    for name, d in named:
+        s = (d[0] * k, d[1] * k)
+        ok = all(-lim <= v <= lim for o, b in boxes for v in move_box(b, d if o else s))
+        if ok:
+            out.append((name, d, s))
+    return out
+
+
+def lined_up(fx, fy, boxes, lim):
+    """Offsets at which a resampler without points finds its source: with 1 / f = p / q the target moves by q n and the
+    source by p n, across the 16-bit lines and as far as the bound lets the larger of the two go."""
+    from fractions import Fraction
+    rx, ry = Fraction(1.0 / fx).limit_denominator(64), Fraction(1.0 / fy).limit_denominator(64)
+    out = []
+    for name, n in (("across +2^15", 2 ** 15 + 1), ("across -2^16", -2 ** 16 - 1), ("far", 2 ** 18 + 1), ("far, negative", -2 ** 18 - 3)):
+        d, s = (rx.denominator * n, -ry.denominator * n), (rx.numerator * n, -ry.numerator * n)
+        if all(-lim <= v <= lim for o, b in boxes for v in move_box(b, d if o else s)):
+            out.append((name, d, s))
+    return out
+
+
+def far_offsets_for(gid, what, boxes):
+    """The far offsets of case `what` of group `gid`, whatever its class: what both far-window modules run it at."""
+    cls, rule = far_class(gid, what)
+    hit = _modelled(gid, what)
+    if hit and hit[0][2] is not None:
+        return lined_up(hit[0][2][0], hit[0][2][1], boxes, rule["limit"])
+    if hit:                                # the scaler: target, source and both points by the same offset
+        return far_offsets(dict(rule, source_scale=1), boxes)
+    return far_offsets(rule, boxes)
+
+
+def odd_dy_offsets(rule, boxes):
+    """Every offset of an even-dy rule one row further (one row back on the top corner): the fields swap."""
+    return [(name + ", dy odd", (d[0], d[1] + (-1 if "top" in name else 1)), (s[0], s[1] + (-1 if "top" in name else 1)))
+            for name, d, s in far_offsets(rule, boxes)]
