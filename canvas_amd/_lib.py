@@ -1,4 +1,4 @@
-"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h).
+"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, include/canvas_scope.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -6,7 +6,7 @@ from here raises, and every pixel entry point needs a HIP device at run time.
 import ctypes as C
 import os
 
-from .abi import (box2i, fir_filter, rational, rgba_frame_f16, rgba_frame_f32, v2f, video_frame_source_funcs,
+from .abi import (box2i, fir_filter, rational, rgba_frame_f16, rgba_frame_f32, v2f, v2i, video_frame_source_funcs,
                   video_source)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,6 +22,8 @@ KEY_SHOW_MATTE = 1                                  # cvs_chroma_key.flags
 MATTE_SHOW, MATTE_MAX_CHOKE, MATTE_MAX_TAPS = 1, 16, 25    # cvs_matte.flags and its limits
 TRANSFORM_NEAREST, TRANSFORM_BILINEAR, TRANSFORM_MAX_COORD = 0, 1, 1 << 23    # cvs_transform.filter and the coordinate limit
 MAX_COORD, RESAMPLE_MAX_COORD = 1 << 30, 1 << 23        # the coordinate contract of canvas_hip.h: every entry's bound, the resamplers'
+SCOPE_HISTOGRAM, SCOPE_WAVEFORM, SCOPE_PARADE, SCOPE_VECTORSCOPE = range(4)      # cvs_scope.kind
+SCOPE_SKIP_TRANSPARENT, SCOPE_MAX_COLUMNS = 1, 4096                             # cvs_scope.flags and the limit of its columns
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
@@ -65,6 +67,17 @@ class transform_params(C.Structure):
 def transform(m=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0), filter=TRANSFORM_BILINEAR):
     """A cvs_transform for the two cvs_transform entries and the window helpers: m maps target to source coordinates."""
     return transform_params((C.c_float * 6)(*[float(v) for v in m]), int(filter), 0)
+
+
+class scope_params(C.Structure):
+    _fields_ = [("kind", C.c_int), ("pre_lut", C.c_int), ("rendering_intent", C.c_float), ("columns", C.c_int), ("flags", C.c_int),
+                ("region", box2i)]
+
+
+def scope(kind, region, columns=256, pre_lut=LUT_NONE, rendering_intent=0.0, flags=0):
+    """A cvs_scope for the scope entries; region: a box2i (copied) or (x0, y0, x1, y1)."""
+    r = region if isinstance(region, box2i) else box2i.of(*region)
+    return scope_params(int(kind), int(pre_lut), float(rendering_intent), int(columns), int(flags), box2i.of(*r.tuple()))
 
 
 class coded_image(C.Structure):
@@ -239,6 +252,15 @@ SIGNATURES = {
     "cvs_mix_cross_f16_dev": (C.c_int, [_F16, _F16, _F16, C.c_float, _vp]),
 }
 
+# the same for include/canvas_scope.h (video scopes): name -> (restype, argtypes), every function that header declares
+SCOPE_SIGNATURES = {
+    "cvs_scope_count": (C.c_size_t, [P(scope_params)]),
+    "cvs_scope_picture_size": (C.c_int, [P(scope_params), P(v2i)]),
+    "cvs_scope_counts_f16_dev": (C.c_int, [_vp, _F16, P(scope_params), _vp]),
+    "cvs_scope_render_f16_dev": (C.c_int, [_F16, P(box2i), _vp, P(scope_params), C.c_float, _vp]),
+    "video_scope_counts": (C.c_int, [_vp, _F16, P(scope_params)]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -265,7 +287,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -74,6 +74,21 @@ static void display_unpin(void *slot) {
     pthread_mutex_unlock(&disp_lock);
 }
 
+/* For the scopes (scope.c; internal.h): the table of (pre_lut, ramp) -- rendering_intent 0 is the gamma-0.45 ramp, > 0 the
+ * widget's -- handed out with disp_lock HELD, or NULL with the error set and the lock released.  cvs_display_table_unlock goes
+ * behind the launch that reads it: under capture (`enqueued`) the graph takes the hold that to_bytes_dev's graphs take. */
+const uint8_t *cvs_display_table_lock(int pre_lut, float rendering_intent, int *slot) {
+    pthread_mutex_lock(&disp_lock);
+    const uint8_t *table = display_table(pre_lut, rendering_intent > 0.0f ? RAMP_INTENT : RAMP_GAMMA45, rendering_intent > 0.0f ? rendering_intent : 0.0f, slot);
+    if (!table) pthread_mutex_unlock(&disp_lock);
+    return table;
+}
+
+void cvs_display_table_unlock(int slot, bool enqueued, hipStream_t s) {
+    if (enqueued && cvs_capture_hold(s, display_unpin, (void *)(intptr_t)(cvs_ctx() * DISP_CACHE + slot))) disp_cache[slot].pins++;
+    pthread_mutex_unlock(&disp_lock);
+}
+
 static int to_bytes_dev(void *dst_dev, const rgba_frame_f16 *frame, int pre_lut, int ramp, float intent, int kmode, hipStream_t s) {
     if (box2i_is_empty(&frame->current_window)) return 0;
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("frame to bytes: current window outside the buffer"); return -1; }

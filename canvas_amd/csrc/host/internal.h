@@ -195,6 +195,13 @@ static inline cvk_dv_planes cvs_planes_view(const coded_image *p) {
     return v;
 }
 
+/* ---- display.c: the display edge's cached 64 KiB byte table of (pre_lut, ramp), for the scopes.  rendering_intent 0: the
+ * gamma-0.45 ramp, > 0: the widget's.  _lock returns the table with the cache's lock HELD (an eviction cannot rewrite it), or
+ * NULL with the error set and the lock released; _unlock goes behind the launch that reads the table and, when that launch was
+ * recorded into a graph on `s` (enqueued), lets the graph hold the table until it is destroyed. */
+const uint8_t *cvs_display_table_lock(int pre_lut, float rendering_intent, int *slot);
+void cvs_display_table_unlock(int slot, bool enqueued, hipStream_t s);
+
 /* device LUT for an id, NULL for CVS_LUT_NONE; builds the tables on first use */
 const half *cvs_lut_dev_or_null(int which);
 /* the table as the separate-arithmetic flavour builds it, whatever the call's flavour (cvs_lut_device follows the flavour:

@@ -293,6 +293,15 @@ int cvk_unsharp_combine(cvk_view out, cvk_view src, cvk_view blurred, cvk_rect r
 enum { CVK_DISPLAY_RGBA8 = 0, CVK_DISPLAY_ARGB32_PREMUL = 1 };
 int cvk_display(void *dst, cvk_view src, cvk_rect r, const uint8_t *table, int mode, int cus, void *stream);
 
+/* scopes (scope_ops.hip): counters over the display bytes of the pixels of `m`, which lies inside `src` and is not empty.
+ * kind: CVS_SCOPE_* of canvas_scope.h.  region_x0, region_w and columns give the output column of a pixel,
+ * (x - region_x0) * columns / region_w (WAVEFORM, PARADE).  `counts` has been zeroed on the same stream. */
+enum { CVK_SCOPE_HISTOGRAM = 0, CVK_SCOPE_WAVEFORM = 1, CVK_SCOPE_PARADE = 2, CVK_SCOPE_VECTORSCOPE = 3 };
+int cvk_scope_counts(uint32_t *counts, cvk_view src, cvk_rect m, const uint8_t *table, int kind, int region_x0, long long region_w,
+                     int columns, int skip_transparent, int cus, void *stream);
+/* the picture of a table: pixels `win` of `out`, the picture's top left pixel at (px0, py0) */
+int cvk_scope_render(cvk_view out, cvk_rect win, int px0, int py0, const uint32_t *counts, int kind, int columns, float gain, void *stream);
+
 /* DV 4:1:1 edge (video_reconstruct.c:50-137, video_subsample.c:99-187): device planes + strides in bytes */
 typedef struct { uint8_t *y, *cb, *cr; int sy, scb, scr; } cvk_dv_planes;
 typedef struct { float coeff[16]; int width, center; } cvk_dv_taps;

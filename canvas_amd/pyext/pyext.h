@@ -11,6 +11,7 @@
 
 #define PY_SSIZE_T_CLEAN
 #include "pyframework.h"
+#include "canvas_scope.h"
 #include <pthread.h>
 
 /* Node locks and the GIL.  Worker threads (pull queue, playback) hold the reader side of a node's rwlock across a pull,
@@ -71,6 +72,13 @@ PyObject *py_get_frame_f16(PyObject *self, PyObject *args, PyObject *kw);
 PyObject *py_get_frame_f32(PyObject *self, PyObject *args, PyObject *kw);
 PyObject *py_get_frame_argb32(PyObject *self, PyObject *args, PyObject *kw);
 PyObject *py_get_frame_rgba8(PyObject *self, PyObject *args, PyObject *kw);
+PyObject *py_get_scope(PyObject *self, PyObject *args, PyObject *kw);
+
+/* the scopes' names and defaults (pyscope.c), shared by the node and by source.get_scope; -1 / false with a ValueError set */
+int py_scope_kind(const char *name);
+int py_scope_display(const char *name);
+bool py_scope_columns_ok(int kind, int columns);
+void py_scope_fill(cvs_scope *p, int kind, int columns, int widget, int skip, const box2i *region);
 
 int init_frames(PyObject *module);
 int init_framefuncs(PyObject *module);
@@ -82,6 +90,7 @@ int init_blur(PyObject *module);
 int init_key(PyObject *module);
 int init_matte(PyObject *module);
 int init_transform(PyObject *module);
+int init_scope(PyObject *module);
 int init_workspace(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */

@@ -166,6 +166,57 @@ static PyObject *pull_bytes(PyObject *self, PyObject *args, PyObject *kw, bool w
 PyObject *py_get_frame_argb32(PyObject *self, PyObject *args, PyObject *kw) { return pull_bytes(self, args, kw, false); }
 PyObject *py_get_frame_rgba8(PyObject *self, PyObject *args, PyObject *kw) { return pull_bytes(self, args, kw, true); }
 
+/* source.get_scope(frame_index, data_window, kind, columns=256, display="export", skip_transparent=False): the frame is pulled
+ * over data_window and counted over it on the device (cvs_scope_counts_f16_dev, region = data_window); what comes back is the
+ * table, native uint32, in 4 bytes per counter -- the only download.  Returns (bytes or None, current_window); None for an
+ * empty data_window.  A source that defines nothing there gives a table of zeros. */
+PyObject *py_get_scope(PyObject *self, PyObject *args, PyObject *kw) {
+    static char *kwlist[] = { "frame_index", "data_window", "kind", "columns", "display", "skip_transparent", NULL };
+    int frame_index, columns = 256, skip = 0;
+    PyObject *window_obj = NULL;
+    const char *kind_name, *display_name = "export";
+    box2i window;
+    if (!PyArg_ParseTupleAndKeywords(args, kw, "iOs|isp", kwlist, &frame_index, &window_obj, &kind_name, &columns, &display_name, &skip)) return NULL;
+    if (!py_parse_box2i(window_obj, &window)) return NULL;
+    const int kind = py_scope_kind(kind_name), widget = kind < 0 ? -1 : py_scope_display(display_name);
+    if (kind < 0 || widget < 0 || !py_scope_columns_ok(kind, columns)) return NULL;
+    cvs_scope p;
+    py_scope_fill(&p, kind, columns, widget, skip, &window);
+    const size_t out = cvs_scope_count(&p) * sizeof(uint32_t);
+    video_source *source = NULL;
+    if (!py_video_take_source(self, &source)) return NULL;
+    PyObject *bytes = NULL, *result = NULL;
+    rgba_frame_dev d = { NULL, CVS_FORMAT_F16, window, window, NULL };
+    void *counts = NULL;
+    int rc = 0;
+    if (box2i_is_empty(&window)) box2i_set_empty(&d.current_window);
+    else if (!(bytes = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)out))) rc = -2;
+    else {
+        char *host = PyBytes_AS_STRING(bytes);
+        const size_t fbytes = frame_bytes(&window, CVS_FORMAT_F16);
+        Py_BEGIN_ALLOW_THREADS
+        d.data = cvs_pool_malloc(fbytes ? fbytes : 1, NULL);
+        counts = cvs_pool_malloc(out, NULL);
+        rc = d.data && counts ? 0 : -1;
+        if (rc == 0) {
+            video_get_frame_dev(source, frame_index, &d);
+            const rgba_frame_f16 f = { d.data, d.full_window, d.current_window };
+            rc = cvs_scope_counts_f16_dev(counts, &f, &p, NULL);
+        }
+        if (rc == 0) rc = cvs_memcpy_d2h(host, counts, out, NULL);
+        Py_END_ALLOW_THREADS
+    }
+    cvs_pool_free(counts, NULL);
+    cvs_pool_free(d.data, NULL);
+    py_video_take_source(NULL, &source);
+    if (rc == -2) return NULL;                       /* Python error already set */
+    if (rc != 0) { Py_XDECREF(bytes); PyErr_SetString(PyExc_RuntimeError, cvs_last_error()); return NULL; }
+    PyObject *win = py_make_box2i(&d.current_window);
+    if (win) result = Py_BuildValue("(ON)", bytes ? bytes : Py_None, win);
+    Py_XDECREF(bytes);
+    return result;
+}
+
 static PyObject *frame16_full(py_frame16 *self, void *c) { return py_make_box2i(&self->frame.full_window); }
 static PyObject *frame16_current(py_frame16 *self, void *c) { return py_make_box2i(&self->frame.current_window); }
 static PyObject *frame32_full(py_frame32 *self, void *c) { return py_make_box2i(&self->frame.full_window); }

@@ -250,6 +250,10 @@ static PyMethodDef VideoSource_methods[] = {
     { "get_frame_rgba8", (PyCFunction)py_get_frame_rgba8, METH_VARARGS | METH_KEYWORDS,
       "(bytearray or None, current_window) = source.get_frame_rgba8(frame_index, data_window, rendering_intent=1.25): "
       "sRGB-encoded r,g,b,a bytes of the defined window, converted on the device (the software widget's display conversion)" },
+    { "get_scope", (PyCFunction)py_get_scope, METH_VARARGS | METH_KEYWORDS,
+      "(bytes or None, current_window) = source.get_scope(frame_index, data_window, kind, columns=256, display=\"export\", "
+      "skip_transparent=False): the uint32 counters of a \"histogram\", \"waveform\", \"parade\" or \"vectorscope\" of the frame over "
+      "data_window, counted on the device from the bytes the export (or the widget) would show" },
     { NULL }
 };
 
@@ -397,7 +401,7 @@ PyMODINIT_FUNC PyInit_process(void) {
     if (import_basetypes() != 0) { Py_DECREF(m); return NULL; }
     init_half();
     if (pyext_add_type(m, "VideoSource", &py_type_VideoSource) < 0 || init_framefuncs(m) < 0 || init_animation(m) < 0 || init_frames(m) < 0 ||
-        init_sources(m) < 0 || init_fields(m) < 0 || init_blur(m) < 0 || init_key(m) < 0 || init_matte(m) < 0 || init_transform(m) < 0 || init_workspace(m) < 0 || init_dv(m) < 0) {
+        init_sources(m) < 0 || init_fields(m) < 0 || init_blur(m) < 0 || init_key(m) < 0 || init_matte(m) < 0 || init_transform(m) < 0 || init_scope(m) < 0 || init_workspace(m) < 0 || init_dv(m) < 0) {
         Py_DECREF(m);
         return NULL;
     }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A small timeline built from the same `fluggo.media.process` objects the Canvas editor creates
 (fluggo/editor/graph/video.py): two clips cut together with a crossfade, a picture-in-picture layer scaled down over
-them, a chroma-keyed layer with its matte refined, a title bar on top.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
+them, a chroma-keyed layer with its matte refined, a title bar on top, an RGB parade of the cut in a corner.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
 
     python examples/timeline.py [out_dir]        # writes frame_000.png ... (and prints Mpx/s)
 """
@@ -62,6 +62,10 @@ title = process.SolidColorVideoSource((0.0, 0.0, 0.0, 0.7), box2i(0, H - 90, W -
 card = process.SolidColorVideoSource((0.2, 0.85, 0.9, 0.9), box2i(0, 0, 479, 269))
 card = process.VideoTransformFilter(card, box2i(0, 0, 479, 269), anchor=(239.5, 134.5), scale=(0.4, 0.4),
                                     rotation=process.LerpFunc((0.0,), (180.0,), FRAMES), position=(160, 120))
+# an RGB parade of the cut underneath, picture in picture: 96 columns per panel (288 x 256) from the bytes the preview shows, moved from
+# (0, 0), where a scope's picture sits, to the lower right above the title
+parade = process.VideoScopeFilter(sequence, "parade", box2i(0, 0, W - 1, H - 1), columns=96, display="widget", gain=1.0 / 64)
+parade = process.VideoTransformFilter(parade, box2i(0, 0, 287, 255), position=(W - 300, H - 360))
 
 timeline = process.VideoWorkspace()
 timeline.add(source=sequence, x=0, length=FRAMES, z=0, offset=0)
@@ -69,6 +73,7 @@ timeline.add(source=pip, x=10, length=40, z=1, offset=0)
 timeline.add(source=keyed, x=0, length=FRAMES, z=2, offset=0)
 timeline.add(source=title, x=0, length=FRAMES, z=3, offset=0)
 timeline.add(source=card, x=0, length=FRAMES, z=4, offset=0)
+timeline.add(source=parade, x=0, length=FRAMES, z=5, offset=0)
 
 window = box2i(0, 0, W - 1, H - 1)
 timeline.get_frame_rgba8(0, window)                       # first use: tables, code objects

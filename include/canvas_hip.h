@@ -73,8 +73,10 @@ typedef struct { float r, g, b, a; } rgba_f32; /* 16 bytes */
  * Where a frame may lie on the canvas (tests/test_far_windows_gpu.py holds every windowed cvs_*_dev entry to it on frames moved
  * up to the bound; DESIGN.md "Coordinates" has the audit behind the value):
  *   - every coordinate of a non-empty full_window, and of a non-empty current_window the entry reads, lies within
- *     +-CVS_MAX_COORD; so does every coordinate of an explicit window an entry does not merely clip (none today: the window of
- *     cvs_fill_solid_* is clipped to the frame by comparisons alone and may be INT_MIN..INT_MAX, "everywhere") and every v2f point.  A
+ *     +-CVS_MAX_COORD; so does every coordinate of an explicit window an entry does not merely clip (the window of
+ *     cvs_fill_solid_* is clipped to the frame by comparisons alone and may be INT_MIN..INT_MAX, "everywhere"; the `place` of
+ *     cvs_scope_render_f16_dev, canvas_scope.h, is clipped to the target and fixes the picture's origin: it may overhang the
+ *     bound by less than the picture's size, and is refused where no pixel of it lies within the bound) and every v2f point.  A
  *     buffer's width and height are computed in 64 bit and must fit an int.  Empty windows are exempt, whatever they hold.
  *   - an entry handed anything else returns -1 with cvs_last_error() naming the entry and the operand, every output's
  *     current_window empty and nothing launched; the video_* entries on host frames refuse the same before they stage a byte.
@@ -308,7 +310,8 @@ CVS_EXPORT void cvs_free(void *dev);
  * handed to a different stream than it was last used on waits for that stream first */
 /* HIP graphs: record a sequence of device-frame calls on a stream once, replay it with one submission (worth it when
  * the sequence is launch-bound: many short kernels on small frames).  The contract, which tests/test_graph_replay_gpu.py holds
- * every cvs_*_dev entry and the workspace's device slot to:
+ * every cvs_*_dev entry of this header and the workspace's device slot to (tests/test_scope_harness_gpu.py holds
+ * the entries of canvas_scope.h to it with the same code):
  *   - capturing thread = calling thread, one capture per thread at a time; between begin and end only `cvs_*_dev` entry points
  *     (and video_get_frame_dev over sources whose device slots make such calls) on the capturing stream.  A call that names
  *     another stream, or none, is not recorded: it runs at once.
