@@ -1,4 +1,5 @@
-"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, include/canvas_scope.h).
+"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes and the 3D LUT, include/canvas_scope.h and
+include/canvas_lut3d.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -24,6 +25,7 @@ TRANSFORM_NEAREST, TRANSFORM_BILINEAR, TRANSFORM_MAX_COORD = 0, 1, 1 << 23    # 
 MAX_COORD, RESAMPLE_MAX_COORD = 1 << 30, 1 << 23        # the coordinate contract of canvas_hip.h: every entry's bound, the resamplers'
 SCOPE_HISTOGRAM, SCOPE_WAVEFORM, SCOPE_PARADE, SCOPE_VECTORSCOPE = range(4)      # cvs_scope.kind
 SCOPE_SKIP_TRANSPARENT, SCOPE_MAX_COLUMNS = 1, 4096                             # cvs_scope.flags and the limit of its columns
+LUT3D_MIN_SIZE, LUT3D_MAX_SIZE = 2, 65                                           # cvs_lut3d.size
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
@@ -78,6 +80,15 @@ def scope(kind, region, columns=256, pre_lut=LUT_NONE, rendering_intent=0.0, fla
     """A cvs_scope for the scope entries; region: a box2i (copied) or (x0, y0, x1, y1)."""
     r = region if isinstance(region, box2i) else box2i.of(*region)
     return scope_params(int(kind), int(pre_lut), float(rendering_intent), int(columns), int(flags), box2i.of(*r.tuple()))
+
+
+class lut3d_params(C.Structure):
+    _fields_ = [("size", C.c_int), ("domain_min", C.c_float * 3), ("domain_max", C.c_float * 3), ("flags", C.c_int)]
+
+
+def lut3d(size, domain_min=(0.0, 0.0, 0.0), domain_max=(1.0, 1.0, 1.0), flags=0):
+    """A cvs_lut3d for the two cvs_lut3d entries: a lattice of size^3 nodes whose ends sit on domain_min and domain_max."""
+    return lut3d_params(int(size), (C.c_float * 3)(*[float(v) for v in domain_min]), (C.c_float * 3)(*[float(v) for v in domain_max]), int(flags))
 
 
 class coded_image(C.Structure):
@@ -261,6 +272,14 @@ SCOPE_SIGNATURES = {
     "video_scope_counts": (C.c_int, [_vp, _F16, P(scope_params)]),
 }
 
+# the same for include/canvas_lut3d.h (3D colour LUT)
+LUT3D_SIGNATURES = {
+    "cvs_lut3d_bytes": (C.c_size_t, [C.c_int]),
+    "cvs_lut3d_pack": (C.c_int, [_f32p, _f32p, C.c_int]),
+    "cvs_lut3d_f16_dev": (C.c_int, [_F16, _F16, _vp, P(lut3d_params), _vp]),
+    "cvs_lut3d_f32_dev": (C.c_int, [_F32, _F32, _vp, P(lut3d_params), _vp]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -287,7 +306,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

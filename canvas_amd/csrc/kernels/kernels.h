@@ -341,6 +341,17 @@ typedef struct {
 } cvk_key_params;
 int cvk_chroma_key(const cvk_key_params *kp, cvk_view out, cvk_view in, cvk_rect w, int half, int cus, void *stream);
 
+/* 3D LUT (lut3d_ops.hip, DESIGN.md "3D LUT"): `w` inside both views, which are of one format and may be the same buffer.
+ * `lattice`: n^3 nodes of 4 floats on a 16-byte boundary, red fastest; host/lut3d.c has checked 2 <= n <= 65 and formed scale[].
+ * One arithmetic flavour, as the chroma key.  n <= 17: the lattice staged in LDS by persistent workgroups (k_lut3d_lds); larger
+ * ones are read through the caches (k_lut3d); the same arithmetic, lanes and row segments in both. */
+typedef struct {
+    const float *lattice;
+    float dmin[3], scale[3];
+    int n;
+} cvk_lut3d_params;
+int cvk_lut3d(const cvk_lut3d_params *lp, cvk_view out, cvk_view in, cvk_rect w, int half, int cus, void *stream);
+
 /* Matte refine (matte_ops.hip, DESIGN.md "Matte refine"): levels, choke and feather of the alpha channel in one launch, colour
  * carried through.  `w` (the window written) inside both views and inside `s`, the source's current window, itself inside `in`;
  * the views are of one format and NOT the same buffer.  What host/matte.c worked out of a cvs_matte: inv = 1 / (white - black)

@@ -91,6 +91,7 @@ int init_key(PyObject *module);
 int init_matte(PyObject *module);
 int init_transform(PyObject *module);
 int init_scope(PyObject *module);
+int init_lut3d(PyObject *module);
 int init_workspace(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */

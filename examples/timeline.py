@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A small timeline built from the same `fluggo.media.process` objects the Canvas editor creates
 (fluggo/editor/graph/video.py): two clips cut together with a crossfade, a picture-in-picture layer scaled down over
-them, a chroma-keyed layer with its matte refined, a title bar on top, an RGB parade of the cut in a corner.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
+them, a chroma-keyed layer with its matte refined, a title bar on top, one clip graded through a 3D LUT, an RGB parade of the cut in a corner.  Every frame is rendered on the GPU; only the 8-bit preview crosses PCIe.
 
     python examples/timeline.py [out_dir]        # writes frame_000.png ... (and prints Mpx/s)
 """
@@ -12,7 +12,7 @@ import time
 import zlib
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fluggo.media import process  # noqa: E402
+from fluggo.media import cube, process  # noqa: E402
 from fluggo.media.basetypes import box2i  # noqa: E402
 
 W, H, FRAMES = 1280, 720, 60
@@ -38,6 +38,15 @@ def clip(start, end, gain):
 
 a = clip((0.8, 0.2, 0.1, 1.0), (0.9, 0.6, 0.1, 1.0), 1.0)
 b = clip((0.1, 0.3, 0.8, 1.0), (0.1, 0.7, 0.6, 1.0), 1.1)
+
+# clip b is graded: a CDL (slope, offset, power) and a little less saturation, baked into a 17-point cube and looked up on the GPU
+def look(r, g, bl):
+    r, g, bl = (max(1.1 * r + 0.02, 0.0) ** 0.9, max(1.0 * g, 0.0) ** 0.95, max(0.9 * bl - 0.01, 0.0) ** 1.05)
+    y = 0.2126 * r + 0.7152 * g + 0.0722 * bl
+    return tuple(y + 0.85 * (c - y) for c in (r, g, bl))
+
+
+b = process.VideoLut3DFilter(b, process.Lut3D(*cube.lattice_from_function(look, 17)))
 
 # cut + crossfade: a for 20 frames, a -> b over 20 frames (an AnimationFunc drives the mix), b for 20 frames
 fade = process.AnimationFunc()
