@@ -165,9 +165,21 @@ int launch(const cvk_matte_params &mp, size_t bytes, hipStream_t st) {
         if (e != hipSuccess) return (int)e;
     }
     const long long cols = (long long)mp.w.x1 - mp.xs + 1, rows = (long long)mp.w.y1 - mp.w.y0 + 1;
-    const dim3 grid((unsigned)((cols + mp.tw - 1) / mp.tw), (unsigned)((rows + mp.th - 1) / mp.th), 1);
-    hipLaunchKernelGGL((k_matte_refine<HALF>), grid, dim3(kThreads), bytes, st, mp);
-    return (int)hipGetLastError();
+    const long long tiles = (rows + mp.th - 1) / mp.th;
+    // a window of any height: bands of at most kMaxGridY rows of tiles, one launch each (a tile stages its own halo from S,
+    // which stays the whole source window, so a band is the same kernel on a window that starts further down)
+    for (long long first = 0; first < tiles; first += kMaxGridY) {
+        const long long n = tiles - first < kMaxGridY ? tiles - first : kMaxGridY;
+        cvk_matte_params band = mp;
+        band.w.y0 = (int)(mp.w.y0 + first * mp.th);
+        const long long last = (long long)band.w.y0 + n * mp.th - 1;
+        band.w.y1 = last < mp.w.y1 ? (int)last : mp.w.y1;
+        const dim3 grid((unsigned)((cols + mp.tw - 1) / mp.tw), (unsigned)n, 1);
+        hipLaunchKernelGGL((k_matte_refine<HALF>), grid, dim3(kThreads), bytes, st, band);
+        const int rc = (int)hipGetLastError();
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -180,7 +192,7 @@ extern "C" int cvk_matte_refine(const cvk_matte_params *in, int half, void *stre
     const int c = mp.ntaps > 0 ? (mp.ntaps - 1) / 2 : 0;
     if (mp.r < 0 || mp.r > 16 || mp.ntaps < 0 || mp.ntaps > 25 || (mp.ntaps > 0 && !(mp.ntaps & 1)) || mp.tw < 64 || (mp.tw & 1) || mp.th < 1) return (int)hipErrorInvalidValue;
     const size_t bytes = cvk_matte_lds_bytes(mp.tw, mp.th, mp.r + c);
-    if (bytes > CVK_MATTE_MAX_LDS || (long long)(mp.w.y1 - mp.w.y0) / mp.th >= 65535) return (int)hipErrorInvalidValue;
+    if (bytes > CVK_MATTE_MAX_LDS) return (int)hipErrorInvalidValue;
     const int xs2 = mp.w.x0 - (int)(((long long)mp.w.x0 - mp.out.fx0) & 1);
     const bool pairs = half && pair_view(mp.out, xs2) && pair_view(mp.in, xs2);
     mp.xs = pairs ? xs2 : mp.w.x0;

@@ -9,6 +9,11 @@
 namespace rowstream {
 
 constexpr int kLanes = 64, kMinSeg = 8, kMaxSeg = 64, kWavesPerCu = 16;
+// the most workgroups the launchers that fold put along y: within hipDeviceProp_t::maxGridSize[1] (65 536 on gfx950).  A window
+// with more rows of workgroups than that is folded -- longer segments, a walk in the kernel, or one launch per band -- never
+// refused (include/canvas_hip.h, the extent contract; DESIGN.md "Extents" has what the runtime does beyond it, and which
+// launchers rest on that).
+constexpr long long kMaxGridY = 65535;
 typedef uint32_t v4 __attribute__((ext_vector_type(4)));
 typedef uint32_t v2 __attribute__((ext_vector_type(2)));
 
@@ -57,7 +62,7 @@ inline Shape shape(const cvk_rect &w, bool pairs, int out_fx0, int cus) {
     const long long waves = (long long)(cus > 0 ? cus : 256) * kWavesPerCu;
     long long seg = (rows * chunks + waves - 1) / waves;
     seg = seg < kMinSeg ? kMinSeg : (seg > kMaxSeg ? kMaxSeg : seg);
-    if ((rows + seg - 1) / seg > 65535) seg = (rows + 65534) / 65535;
+    if ((rows + seg - 1) / seg > kMaxGridY) seg = (rows + kMaxGridY - 1) / kMaxGridY;     // (from 65 535 x 64 + 1 rows on)
     s.seg = (int)seg;
     s.grid = dim3((unsigned)chunks, (unsigned)((rows + seg - 1) / seg), 1);
     return s;

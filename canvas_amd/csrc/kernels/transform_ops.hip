@@ -35,6 +35,7 @@ namespace {
 using rowstream::v2;
 using rowstream::v4;
 using rowstream::rect_empty;
+using rowstream::kMaxGridY;
 
 constexpr int kThreads = 256;
 typedef v4 v4_align8 __attribute__((aligned(8)));
@@ -136,9 +137,21 @@ __global__ __launch_bounds__(kThreads) void k_transform(cvk_transform_params tp)
 template <int HALF, int BILINEAR, int PAIR>
 int launch(const cvk_transform_params &tp, hipStream_t st) {
     const long long cols = (long long)tp.w.x1 - tp.w.x0 + 1, rows = (long long)tp.w.y1 - tp.w.y0 + 1;
-    const dim3 grid((unsigned)((cols + tp.tw - 1) / tp.tw), (unsigned)((rows + tp.th - 1) / tp.th), 1);
-    hipLaunchKernelGGL((k_transform<HALF, BILINEAR, PAIR>), grid, dim3(kThreads), 0, st, tp);
-    return (int)hipGetLastError();
+    const long long tiles = (rows + tp.th - 1) / tp.th;
+    // a window of any height: bands of at most kMaxGridY rows of tiles, one launch each (a tile depends on nothing but its
+    // own coordinates, so a band is the same kernel on a window that starts further down)
+    for (long long first = 0; first < tiles; first += kMaxGridY) {
+        const long long n = tiles - first < kMaxGridY ? tiles - first : kMaxGridY;
+        cvk_transform_params band = tp;
+        band.w.y0 = (int)(tp.w.y0 + first * tp.th);
+        const long long last = (long long)band.w.y0 + n * tp.th - 1;
+        band.w.y1 = last < tp.w.y1 ? (int)last : tp.w.y1;
+        const dim3 grid((unsigned)((cols + tp.tw - 1) / tp.tw), (unsigned)n, 1);
+        hipLaunchKernelGGL((k_transform<HALF, BILINEAR, PAIR>), grid, dim3(kThreads), 0, st, band);
+        const int rc = (int)hipGetLastError();
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -147,7 +160,6 @@ extern "C" int cvk_transform(const cvk_transform_params *in, int half, void *str
     const cvk_transform_params &tp = *in;
     if (rect_empty(tp.w)) return 0;
     if (rect_empty(tp.s) || tp.tw < 8 || tp.tw > kThreads || (tp.tw & (tp.tw - 1)) || tp.tw * tp.th != kThreads) return (int)hipErrorInvalidValue;
-    if (((long long)tp.w.y1 - tp.w.y0) / tp.th >= 65535) return (int)hipErrorInvalidValue;
     // the window written inside the target's buffer, the source window inside the source's: nothing else is ever addressed
     if (tp.w.x0 < tp.out.fx0 || tp.w.y0 < tp.out.fy0 || tp.w.x1 > tp.out.fx1 || tp.w.y1 > tp.out.fy1) return (int)hipErrorInvalidValue;
     if (tp.s.x0 < tp.in.fx0 || tp.s.y0 < tp.in.fy0 || tp.s.x1 > tp.in.fx1 || tp.s.y1 > tp.in.fy1) return (int)hipErrorInvalidValue;

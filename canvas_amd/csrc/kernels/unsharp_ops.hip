@@ -219,6 +219,8 @@ extern "C" int cvk_unsharp(const cvk_unsharp_params *up, int cus, void *stream) 
 extern "C" int cvk_unsharp_combine(cvk_view out, cvk_view src, cvk_view blurred, cvk_rect r, int half, float amount, float threshold, void *stream) {
     if (r.x1 < r.x0 || r.y1 < r.y0) return 0;
     const long long cols = (long long)r.x1 - r.x0 + 1, rows = (long long)r.y1 - r.y0 + 1;
+    // at most 32 768 workgroups along y, the rows beyond walked in the kernel: a fold kept as defence (the runtime was measured
+    // to take grid.y = rows past 65 535, DESIGN.md "Extents"); tests/test_extents_gpu.py runs it at 65 535, 65 536 and 70 001 rows
     dim3 grid((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768), 1);
     if (half) hipLaunchKernelGGL(k_unsharp_combine<true>, grid, dim3(256), 0, (hipStream_t)stream, out, src, blurred, r, amount, threshold);
     else hipLaunchKernelGGL(k_unsharp_combine<false>, grid, dim3(256), 0, (hipStream_t)stream, out, src, blurred, r, amount, threshold);

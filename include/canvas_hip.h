@@ -84,7 +84,21 @@ typedef struct { float r, g, b, a; } rgba_f32; /* 16 bytes */
  *     exact: the bound leaves 2^30 - 1 of headroom and the largest such sum adds a few thousand.
  *   - the entries that form positions in `float`, as the reference's v2f interface does, hold a tighter bound of their own,
  *     inside which a float holds every integer: CVS_TRANSFORM_MAX_COORD for cvs_transform_*, CVS_RESAMPLE_MAX_COORD for the
- *     bilinear scaler and the Lanczos resamplers (their windows; the points they are handed lie within it as well). */
+ *     bilinear scaler and the Lanczos resamplers (their windows; the points they are handed lie within it as well).
+ *
+ * How tall or wide a window may be (tests/test_extents_gpu.py holds the frame-taking cvs_*_dev entries to it at 65 535,
+ * 65 536 and 70 001 rows, at 70 001 and 131 073 columns and at the row counts where a launcher's own arithmetic changes;
+ * DESIGN.md "Extents" has the launcher-by-launcher table):
+ *   - ANY extent.  Every entry computes any non-empty window the coordinate bounds above admit, whatever its height and
+ *     width: a strip two pixels wide and 70 001 rows tall, a scan line 131 073 pixels long are legal frames.  There is no
+ *     limit on the rows or columns of a window beside those bounds and the memory behind the buffer (a frame beyond 4 GiB is
+ *     out of scope), and no entry refuses a window for its size.  How the launchers get there differs: the row
+ *     streams, the unsharp combine, the transform and the matte keep to 65 535 workgroups along y and fold the rest (longer
+ *     segments, a walk inside the kernel, one launch per band); the others (copies, conversions, fills, gain, the f32 mixers, the
+ *     weave, the table FIR passes, the enlarging scaler's tiles) launch one row of workgroups per row, or per segment of
+ *     rows, of the window and rest on the HIP runtime taking more of them than hipDeviceProp_t::maxGridSize[1] states, which
+ *     it does on gfx950 (measured to 1 048 577).  A runtime that refused such a launch would make the entry fail with its
+ *     message, not compute wrong pixels. */
 enum { CVS_MAX_COORD = 1 << 30, CVS_RESAMPLE_MAX_COORD = 1 << 23 };
 typedef struct { rgba_f16 *data; box2i full_window; box2i current_window; } rgba_frame_f16;
 typedef struct { rgba_f32 *data; box2i full_window; box2i current_window; } rgba_frame_f32;

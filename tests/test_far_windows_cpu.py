@@ -6,13 +6,9 @@ stand-in library that hands cvs_X_dev(..., stream) to orc_X(...) on frames in ho
 entry_cases.Shifted at every offset the GPU module uses for that case: an equivariant case must give the origin's bytes and
 windows, a modelled one must run and stay inside its buffers.  The Python models the other GPU modules tie the remaining
 entries to (fields, key, matte, unsharp, transform) are evaluated the same way on a small frame each."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import oracle
-from canvas_amd.abi import HostFrame
 from tests import entry_cases as ec
 from tests import fields_model as fm
 from tests import key_model as km
@@ -20,128 +16,12 @@ from tests import matte_model as mm
 from tests import transform_model as tm
 from tests import unsharp_model as um
 from tests.models import f2h_rz_model
+from tests.reference_library import NotInTheOracle, OnHost, OracleAsLibrary      # (shared with tests/test_extents_*.py)
 from tests.util import same_window
 
-# device entry -> the oracle function with the same arguments but the stream
-ORACLE = {"cvs_copy_frame_f16_dev": "orc_copy_frame_f16", "cvs_copy_frame_alpha_f32_dev": "orc_copy_frame_alpha_f32",
-          "cvs_gain_offset_f16_dev": "orc_gain_offset_f16", "cvs_mix_over_f32_dev": "orc_mix_over_f32",
-          "cvs_mix_cross_f32_dev": "orc_mix_cross_f32", "cvs_weave_fields_f16_dev": "orc_weave_fields_f16",
-          "cvs_scale_bilinear_f32_dev": "orc_scale_bilinear_f32", "cvs_resample_lanczos_f32_dev": "orc_resample_lanczos_f32",
-          "cvs_fir_blur_f32_dev": "orc_fir_blur_f32"}
 # Offsets taken out for one group, by name, because the reference's own `int` code is undefined there: (group prefix, offset
 # name) -> why.  None today.
 ORACLE_UNDEFINED = {}
-
-
-class NotInTheOracle(Exception):
-    pass
-
-
-def _struct(ref):
-    return getattr(ref, "_obj", ref)
-
-
-def _pixels_of(c, dtype):
-    """The numpy view of the buffer a frame struct describes."""
-    h, w = c.full_window.height, c.full_window.width
-    ctype = C.c_uint16 if dtype == np.uint16 else C.c_float
-    return np.ctypeslib.as_array(C.cast(c.data, C.POINTER(ctype)), shape=(h, w, 4))
-
-
-def _widened(c):
-    """A half frame struct as the f32 HostFrame its f32 pull would deliver (tests/test_gpu_parity.py: widen, then the f32 node)."""
-    return HostFrame(c.full_window.tuple(), np.float32, oracle.half_to_float(_pixels_of(c, np.uint16)), c.current_window.tuple())
-
-
-def _narrow_into(c, f32, window_only):
-    """... and the f32 result truncated into the half frame: the whole buffer, or (window_only, the scaler: what lies outside
-    the reported window is not defined) the reported window alone."""
-    codes = oracle.float_to_half(f32.array)
-    w, full = f32.current_window, c.full_window
-    if not window_only:
-        _pixels_of(c, np.uint16)[...] = codes
-    elif not w.is_empty():
-        ys, xs = slice(w.min.y - full.min.y, w.max.y - full.min.y + 1), slice(w.min.x - full.min.x, w.max.x - full.min.x + 1)
-        _pixels_of(c, np.uint16)[ys, xs] = codes[ys, xs]
-    c.current_window = type(c.current_window).of(*w.tuple())
-
-
-# The f16 and batch forms of the resamplers, composed of the oracle's f32 pieces as tests/test_gpu_parity.py composes them
-# (test_scale_bilinear_f16_twin, test_lanczos_resample_between_f16_frames, _oracle_config3); a batch is its single calls.
-def _lanczos_f16(out, src, fx, fy, ksize):
-    o, t = _struct(out), HostFrame(_struct(out).full_window.tuple(), np.float32)
-    s32 = _widened(_struct(src))
-    oracle.lib().orc_resample_lanczos_f32(t.ref(), s32.ref(), fx, fy, ksize)
-    _narrow_into(o, t, False)
-
-
-def _scale_f16(out, tp, src, sp, fac):
-    o = _struct(out)
-    t, s32 = _widened(o), _widened(_struct(src))
-    oracle.lib().orc_scale_bilinear_f32(t.ref(), tp, s32.ref(), sp, fac)
-    _narrow_into(o, t, True)
-
-
-def _scale_batch(half):
-    def run(outs, tp, srcs, sp, fac, count):
-        for k in range(count):
-            if half:
-                _scale_f16(outs[k].contents, tp, srcs[k].contents, sp, fac)
-            else:
-                oracle.lib().orc_scale_bilinear_f32(outs[k], tp, srcs[k], sp, fac)
-    return run
-
-
-def _blur_lanczos_f16(out, src, taps, ntaps, fx, fy, ksize):
-    o, s32 = _struct(out), _widened(_struct(src))
-    blurred = HostFrame(s32.full_window.tuple(), np.float32)
-    oracle.lib().orc_fir_blur_f32(blurred.ref(), s32.ref(), taps, ntaps)
-    t = HostFrame(o.full_window.tuple(), np.float32)
-    oracle.lib().orc_resample_lanczos_f32(t.ref(), blurred.ref(), fx, fy, ksize)
-    _narrow_into(o, t, False)
-
-
-def _blur_lanczos_batch(outs, srcs, count, taps, ntaps, fx, fy, ksize):
-    for k in range(count):
-        _blur_lanczos_f16(outs[k].contents, srcs[k].contents, taps, ntaps, fx, fy, ksize)
-
-
-COMPOSED = {"cvs_resample_lanczos_f16_dev": _lanczos_f16, "cvs_scale_bilinear_f16_dev": _scale_f16,
-            "cvs_scale_bilinear_f16_batch_dev": _scale_batch(True), "cvs_scale_bilinear_f32_batch_dev": _scale_batch(False),
-            "cvs_blur_lanczos_f16_dev": _blur_lanczos_f16, "cvs_blur_lanczos_f16_batch_dev": _blur_lanczos_batch}
-# the entries whose oracle result is defined inside the reported window only
-WINDOW_ONLY = ("cvs_scale_bilinear_f16_dev", "cvs_scale_bilinear_f16_batch_dev")
-
-
-class OracleAsLibrary:
-    """Stands in for the library: the entries of ORACLE run the oracle's function, those of COMPOSED the oracle's pieces; any
-    other raises NotInTheOracle."""
-
-    def __getattr__(self, name):
-        if name not in ORACLE and name not in COMPOSED:
-            def missing(*args):
-                raise NotInTheOracle(name)
-            return missing
-        fn = COMPOSED[name] if name in COMPOSED else getattr(oracle.lib(), ORACLE[name])
-
-        def call(*args):
-            fn(*args[:-1])
-            return 0
-        return call
-
-
-class OnHost(ec.Factory):
-    """Frames in host memory, each with pixels of its own."""
-
-    def _make_frame(self, o, host):
-        o.frame = HostFrame(host.full_window.tuple(), host.dtype, host.array.copy(), host.current_window.tuple())
-        o.ptr = o.frame.array.ctypes.data
-
-    def _make_buffer(self, o, data):
-        raise NotInTheOracle("a flat buffer")
-
-    def collect(self):
-        return [o.frame.array.copy() for o in self.objects]
 
 
 def _oracle_cases():

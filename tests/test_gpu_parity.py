@@ -1374,7 +1374,9 @@ def _blur_over(cvs, out_full, src, taps, overlays):
     d_src = DeviceFrame.from_host(src)
     d_ov = [DeviceFrame.from_host(o) for o in overlays]
     refs = (C.POINTER(_lib.rgba_frame_f16_t) * max(len(d_ov), 1))(*[C.pointer(o.c) for o in d_ov])
-    d_out = DeviceFrame(out_full, np.uint16)
+    # (zeros uploaded, not a bare allocation: callers compare whole buffers of two calls, and what a fresh allocation holds
+    # outside the window written is whatever the block held before)
+    d_out = DeviceFrame.from_host(HostFrame(out_full, np.uint16))
     _lib.check(cvs.cvs_blur_over_f16_dev(d_out.ref(), d_src.ref(), f32p(taps), len(taps), refs, len(d_ov), None))
     return d_out.download()
 
