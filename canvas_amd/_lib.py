@@ -1,5 +1,5 @@
-"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes and the 3D LUT, include/canvas_scope.h and
-include/canvas_lut3d.h).
+"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT and the corner pin,
+include/canvas_scope.h, include/canvas_lut3d.h and include/canvas_perspective.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -26,6 +26,7 @@ MAX_COORD, RESAMPLE_MAX_COORD = 1 << 30, 1 << 23        # the coordinate contrac
 SCOPE_HISTOGRAM, SCOPE_WAVEFORM, SCOPE_PARADE, SCOPE_VECTORSCOPE = range(4)      # cvs_scope.kind
 SCOPE_SKIP_TRANSPARENT, SCOPE_MAX_COLUMNS = 1, 4096                             # cvs_scope.flags and the limit of its columns
 LUT3D_MIN_SIZE, LUT3D_MAX_SIZE = 2, 65                                           # cvs_lut3d.size
+PERSPECTIVE_MAX_SPAN = 1 << 23                                                   # cvs_perspective: how far a window may lie from its origin
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
 
@@ -89,6 +90,17 @@ class lut3d_params(C.Structure):
 def lut3d(size, domain_min=(0.0, 0.0, 0.0), domain_max=(1.0, 1.0, 1.0), flags=0):
     """A cvs_lut3d for the two cvs_lut3d entries: a lattice of size^3 nodes whose ends sit on domain_min and domain_max."""
     return lut3d_params(int(size), (C.c_float * 3)(*[float(v) for v in domain_min]), (C.c_float * 3)(*[float(v) for v in domain_max]), int(flags))
+
+
+class perspective_params(C.Structure):
+    _fields_ = [("h", C.c_float * 9), ("target_origin", C.c_int * 2), ("source_origin", C.c_int * 2), ("filter", C.c_int), ("flags", C.c_int)]
+
+
+def perspective(h=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), target_origin=(0, 0), source_origin=(0, 0), filter=TRANSFORM_BILINEAR, flags=0):
+    """A cvs_perspective for the two cvs_perspective entries and the window helpers: h maps target to source coordinates, each
+    side counted from its origin."""
+    return perspective_params((C.c_float * 9)(*[float(v) for v in h]), (C.c_int * 2)(*[int(v) for v in target_origin]),
+                              (C.c_int * 2)(*[int(v) for v in source_origin]), int(filter), int(flags))
 
 
 class coded_image(C.Structure):
@@ -280,6 +292,15 @@ LUT3D_SIGNATURES = {
     "cvs_lut3d_f32_dev": (C.c_int, [_F32, _F32, _vp, P(lut3d_params), _vp]),
 }
 
+# the same for include/canvas_perspective.h (corner pin)
+PERSPECTIVE_SIGNATURES = {
+    "cvs_perspective_f32_dev": (C.c_int, [_F32, _F32, P(perspective_params), _vp]),
+    "cvs_perspective_f16_dev": (C.c_int, [_F16, _F16, P(perspective_params), _vp]),
+    "cvs_perspective_from_quad": (C.c_int, [P(C.c_double), P(C.c_double * 2), C.c_int, P(perspective_params)]),
+    "cvs_perspective_target_window": (C.c_int, [P(perspective_params), P(box2i), P(box2i), P(box2i)]),
+    "cvs_perspective_source_window": (C.c_int, [P(perspective_params), P(box2i), P(box2i)]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -306,7 +327,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

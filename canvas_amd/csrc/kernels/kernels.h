@@ -386,6 +386,20 @@ typedef struct {
 } cvk_transform_params;
 int cvk_transform(const cvk_transform_params *tp, int half, void *stream);
 
+/* Corner pin (perspective_ops.hip, DESIGN.md "Corner pin"): coordinates RELATIVE to the two origins of the cvs_perspective.
+ * `w`: the window written minus the target origin, `s`: the source's current window (not empty) minus the source origin, every
+ * coordinate of both within +-2^23; tdx, tdy / sdx, sdy: the origin minus the view's first pixel, so that relative pixel (x, y)
+ * is column tdx + x of row tdy + y of `out` (sdx, sdy: of `in`), with `w` inside `out` and `s` inside `in` that way.  The
+ * views are of one format and NOT the same buffer.  h maps relative target to relative source coordinates.  Tiles of 32 x 8. */
+typedef struct {
+    cvk_view out, in;
+    cvk_rect w, s;
+    long long tdx, tdy, sdx, sdy;
+    float h[9];
+    int bilinear;              /* else nearest */
+} cvk_perspective_params;
+int cvk_perspective(const cvk_perspective_params *pp, int half, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

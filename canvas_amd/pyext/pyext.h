@@ -65,6 +65,11 @@ extern PyMethodDef node1_methods[];
 /* a source that fills the f16 host slot only is half-native: its f32 pull is "pull f16, widen" (main.c:105-144) */
 static inline bool half_native(const video_source *src) { return src && src->funcs && src->funcs->get_frame && !src->funcs->get_frame_32; }
 
+/* shared by the geometry nodes (pytransform.c): "nearest" / "bilinear" -> CVS_TRANSFORM_*, or -1 with a Python error set;
+ * transparent black over a box of `f`, its window left alone: 0, or -1 */
+int py_transform_filter_from(PyObject *v);
+int py_clear_box(rgba_frame_dev *f, int x0, int y0, int x1, int y1);
+
 /* frame objects (pyframes.c) */
 PyObject *py_RgbaFrameF16_new(box2i *full_window, rgba_frame_f16 **frame);
 PyObject *py_RgbaFrameF32_new(box2i *full_window, rgba_frame_f32 **frame);
@@ -92,6 +97,7 @@ int init_matte(PyObject *module);
 int init_transform(PyObject *module);
 int init_scope(PyObject *module);
 int init_lut3d(PyObject *module);
+int init_perspective(PyObject *module);
 int init_workspace(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */

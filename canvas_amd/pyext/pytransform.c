@@ -58,7 +58,7 @@ static void part_install(py_transform *self, int k, PyObject *v, FrameFunctionHo
     Py_XDECREF(old_given);
 }
 
-static int filter_from(PyObject *v) {
+int py_transform_filter_from(PyObject *v) {
     if (v && PyUnicode_Check(v)) {
         if (PyUnicode_CompareWithASCIIString(v, "nearest") == 0) return CVS_TRANSFORM_NEAREST;
         if (PyUnicode_CompareWithASCIIString(v, "bilinear") == 0) return CVS_TRANSFORM_BILINEAR;
@@ -77,7 +77,7 @@ static int transform_init(py_transform *self, PyObject *args, PyObject *kw) {
     for (int k = 0; k < PART_COUNT; k++) framefunc_init(&self->part[k], 0, 0, 0, 0);
     if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|OOOOO", kwlist, &src, &given[PART_RECT], &given[PART_ANCHOR], &given[PART_SCALE],
                                      &given[PART_ROTATION], &given[PART_POSITION], &filter)) return -1;
-    if (filter && (self->filter = filter_from(filter)) < 0) return -1;
+    if (filter && (self->filter = py_transform_filter_from(filter)) < 0) return -1;
     PyObject *defaults[PART_COUNT] = { NULL, Py_BuildValue("(dd)", 0.0, 0.0), Py_BuildValue("(dd)", 1.0, 1.0), PyFloat_FromDouble(0.0), Py_BuildValue("(dd)", 0.0, 0.0) };
     bool ok = true;
     for (int k = 0; k < PART_COUNT; k++) {
@@ -108,7 +108,7 @@ static int coefficients(py_transform *self, int frame_index, float m[6]) {
 }
 
 /* transparent black over `box` of `f` (its window is left alone): 0, or -1 */
-static int clear_box(rgba_frame_dev *f, int x0, int y0, int x1, int y1) {
+int py_clear_box(rgba_frame_dev *f, int x0, int y0, int x1, int y1) {
     static const rgba_f32 nothing = { 0.0f, 0.0f, 0.0f, 0.0f };
     box2i box;
     box2i_set(&box, x0, y0, x1, y1);
@@ -128,14 +128,14 @@ static int clear_box(rgba_frame_dev *f, int x0, int y0, int x1, int y1) {
 static int fill_layer(rgba_frame_dev *f, const box2i *layer) {
     box2i win = f->current_window, all = *layer;
     if (box2i_is_empty(&all)) return 0;
-    if (box2i_is_empty(&win)) { f->current_window = all; return clear_box(f, all.min.x, all.min.y, all.max.x, all.max.y); }
+    if (box2i_is_empty(&win)) { f->current_window = all; return py_clear_box(f, all.min.x, all.min.y, all.max.x, all.max.y); }
     if (win.min.x < all.min.x) all.min.x = win.min.x;
     if (win.min.y < all.min.y) all.min.y = win.min.y;
     if (win.max.x > all.max.x) all.max.x = win.max.x;
     if (win.max.y > all.max.y) all.max.y = win.max.y;
     f->current_window = all;
-    if (clear_box(f, all.min.x, all.min.y, all.max.x, win.min.y - 1) != 0 || clear_box(f, all.min.x, win.max.y + 1, all.max.x, all.max.y) != 0) return -1;
-    if (clear_box(f, all.min.x, win.min.y, win.min.x - 1, win.max.y) != 0 || clear_box(f, win.max.x + 1, win.min.y, all.max.x, win.max.y) != 0) return -1;
+    if (py_clear_box(f, all.min.x, all.min.y, all.max.x, win.min.y - 1) != 0 || py_clear_box(f, all.min.x, win.max.y + 1, all.max.x, all.max.y) != 0) return -1;
+    if (py_clear_box(f, all.min.x, win.min.y, win.min.x - 1, win.max.y) != 0 || py_clear_box(f, win.max.x + 1, win.min.y, all.max.x, win.max.y) != 0) return -1;
     return 0;
 }
 
@@ -220,7 +220,7 @@ static PyObject *transform_get_filter(py_transform *self, void *closure) {
     return PyUnicode_FromString(self->filter == CVS_TRANSFORM_NEAREST ? "nearest" : "bilinear");
 }
 static int transform_set_filter(py_transform *self, PyObject *v, void *closure) {
-    const int filter = filter_from(v);
+    const int filter = py_transform_filter_from(v);
     if (filter < 0) return -1;
     py_wrlock_nogil(&self->n.lock);
     self->filter = filter;
