@@ -1,5 +1,6 @@
-"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT and the corner pin,
-include/canvas_scope.h, include/canvas_lut3d.h and include/canvas_perspective.h).
+"""ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
+and the adaptive deinterlacer, include/canvas_scope.h, include/canvas_lut3d.h, include/canvas_perspective.h and
+include/canvas_deinterlace.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -101,6 +102,15 @@ def perspective(h=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), target_origin=(
     side counted from its origin."""
     return perspective_params((C.c_float * 9)(*[float(v) for v in h]), (C.c_int * 2)(*[int(v) for v in target_origin]),
                               (C.c_int * 2)(*[int(v) for v in source_origin]), int(filter), int(flags))
+
+
+class deinterlace_params(C.Structure):
+    _fields_ = [("field", C.c_int), ("threshold", C.c_float), ("softness", C.c_float), ("flags", C.c_int)]
+
+
+def deinterlace_adaptive(field=0, threshold=0.02, softness=0.04, flags=0):
+    """A cvs_deinterlace_adaptive for cvs_deinterlace_adaptive_f16_dev."""
+    return deinterlace_params(int(field), float(threshold), float(softness), int(flags))
 
 
 class coded_image(C.Structure):
@@ -301,6 +311,11 @@ PERSPECTIVE_SIGNATURES = {
     "cvs_perspective_source_window": (C.c_int, [P(perspective_params), P(box2i), P(box2i)]),
 }
 
+# the same for include/canvas_deinterlace.h (motion-adaptive deinterlace)
+DEINTERLACE_SIGNATURES = {
+    "cvs_deinterlace_adaptive_f16_dev": (C.c_int, [_F16, _F16, _F16, _F16, P(deinterlace_params), _vp]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -327,7 +342,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

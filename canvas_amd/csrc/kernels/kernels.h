@@ -400,6 +400,21 @@ typedef struct {
 } cvk_perspective_params;
 int cvk_perspective(const cvk_perspective_params *pp, int half, void *stream);
 
+/* Motion-adaptive deinterlace (deinterlace_ops.hip, DESIGN.md "Adaptive deinterlace"), f16 frames.  `w` (the window written)
+ * inside `out` and inside `cw`, cur's current window, itself inside `cur`.  n[j], j < neighbours (1 or 2): the neighbour frames
+ * that are present, in either order; v[j] = cw ∩ the neighbour's current window (not empty, inside n[j]): where a sample of
+ * that neighbour counts.  No view is `out`'s buffer.  What host/deinterlace.c worked out of a cvs_deinterlace_adaptive:
+ * soft = softness > 0, inv_soft = 1 / softness (read only where soft).  The launcher sets xs and seg.  One arithmetic flavour:
+ * every operation is rounded on its own in both (the unit is not rebuilt with -DCVS_CONTRACT). */
+typedef struct {
+    cvk_view out, cur, n[2];
+    cvk_rect w, cw, v[2];
+    int field, soft;
+    float threshold, inv_soft;
+    int xs, seg;               /* column of lane 1 of the first workgroup (w.x0 or the pair boundary left of it); rows per segment */
+} cvk_deinterlace_params;
+int cvk_deinterlace_adaptive(const cvk_deinterlace_params *dp, int neighbours, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

@@ -1,4 +1,4 @@
-// stream_common.hpp -- pieces shared by the row streams (field_ops.hip, key_ops.hip): a one-wave workgroup owns 64 lanes x PIX
+// stream_common.hpp -- pieces shared by the row streams (field_ops.hip, key_ops.hip, deinterlace_ops.hip): a one-wave workgroup owns 64 lanes x PIX
 // columns over a segment of consecutive rows and walks down them.  Half RGBA pixels are 8 bytes; two per lane are one 16-byte
 // access where every buffer involved puts the same column pairs on 16-byte boundaries (pair_view), one per lane otherwise.
 #pragma once
@@ -52,13 +52,14 @@ inline bool pair_view(const cvk_view &v, int xs) {
 struct Shape { int pix, xs, seg; dim3 grid; };
 
 // segments: enough one-wave workgroups for kWavesPerCu waves on every CU where the window has the rows for it, never shorter than
-// kMinSeg rows (a kernel with a vertical window reads its seam rows twice)
-inline Shape shape(const cvk_rect &w, bool pairs, int out_fx0, int cus) {
+// kMinSeg rows (a kernel with a vertical window reads its seam rows twice).  `made`: the lanes of a wave that make columns (fewer
+// than kLanes where the outermost lanes only load a neighbour's column and hand it on: deinterlace_ops.hip)
+inline Shape shape(const cvk_rect &w, bool pairs, int out_fx0, int cus, int made = kLanes) {
     Shape s;
     s.pix = pairs ? 2 : 1;
     s.xs = pairs ? w.x0 - (int)(((long long)w.x0 - out_fx0) & 1) : w.x0;
     const long long cols = (long long)w.x1 - s.xs + 1, rows = (long long)w.y1 - w.y0 + 1;
-    const long long chunks = (cols + s.pix * kLanes - 1) / (s.pix * kLanes);
+    const long long chunks = (cols + s.pix * made - 1) / (s.pix * made);
     const long long waves = (long long)(cus > 0 ? cus : 256) * kWavesPerCu;
     long long seg = (rows * chunks + waves - 1) / waves;
     seg = seg < kMinSeg ? kMinSeg : (seg > kMaxSeg ? kMaxSeg : seg);

@@ -91,6 +91,7 @@ int init_animation(PyObject *module);
 int init_dv(PyObject *module);
 int init_sources(PyObject *module);
 int init_fields(PyObject *module);
+int init_deint(PyObject *module);
 int init_blur(PyObject *module);
 int init_key(PyObject *module);
 int init_matte(PyObject *module);
