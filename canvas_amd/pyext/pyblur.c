@@ -107,19 +107,7 @@ static void blur_render(PyObject *o, int frame_index, rgba_frame_dev *f) {
     cvs_pool_free(in.data, f->stream);
 }
 
-static void blur_slot_dev(PyObject *o, int i, rgba_frame_dev *f) {
-    py_blur *self = (py_blur *)o;
-    py_rdlock(&self->n.lock);
-    const bool direct = f->format == CVS_FORMAT_F16 && half_native(self->n.source);
-    pthread_rwlock_unlock(&self->n.lock);
-    if (direct) blur_render(o, i, f);                   /* widen, both passes (and the mask), truncate: one launch */
-    else node_get_frame_dev(o, i, f, CVS_FORMAT_F32, blur_render);
-}
-static void blur_slot_32(PyObject *o, int i, rgba_frame_f32 *f) { node_get_frame_host32(o, i, f, CVS_FORMAT_F32, blur_render); }
-static video_frame_source_funcs blur_funcs = {
-    .flags = VIDEO_SOURCE_FLAG_DEVICE, .get_frame_32 = (video_get_frame_32_func)blur_slot_32,
-    .get_frame_dev = (video_get_frame_dev_func)blur_slot_dev };
-static PyObject *blur_capsule;
+DEFINE_NODE_VTABLE_HALF_DIRECT(blur)                  /* widen, both passes (and the mask), truncate: one launch */
 
 static PyObject *blur_get_taps(py_blur *self, void *c) {
     py_rdlock(&self->n.lock);
@@ -143,21 +131,11 @@ static int blur_set_taps(py_blur *self, PyObject *value, void *c) {
     free(old);
     return 0;
 }
-static PyObject *holder_get(FrameFunctionHolder *h) {
-    if (h->source) { Py_INCREF(h->source); return h->source; }
-    return PyFloat_FromDouble(h->constant[0]);
-}
-static int holder_set(py_blur *self, FrameFunctionHolder *h, PyObject *v) {
+static int unsharp_set_holder(py_blur *self, PyObject *v, void *offset) {
     if (!v) { PyErr_SetString(PyExc_TypeError, "cannot delete the attribute"); return -1; }
-    py_wrlock_nogil(&self->n.lock);
-    const bool ok = py_framefunc_take_source(v, h);
-    pthread_rwlock_unlock(&self->n.lock);
-    return ok ? 0 : -1;
+    if (v == Py_None) { PyErr_SetString(PyExc_TypeError, "the attribute takes a number or a frame function"); return -1; }
+    return node1_set_holder(&self->n, NODE1_HOLDER_AT(self, offset), v);
 }
-static PyObject *unsharp_get_amount(py_blur *self, void *c) { return holder_get(&self->amount); }
-static PyObject *unsharp_get_threshold(py_blur *self, void *c) { return holder_get(&self->threshold); }
-static int unsharp_set_amount(py_blur *self, PyObject *v, void *c) { return holder_set(self, &self->amount, v); }
-static int unsharp_set_threshold(py_blur *self, PyObject *v, void *c) { return holder_set(self, &self->threshold, v); }
 
 static PyGetSetDef blur_getset[] = {
     { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &blur_capsule },
@@ -169,8 +147,8 @@ static PyGetSetDef unsharp_getset[] = {
     { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &blur_capsule },
     { "source", (getter)node1_get_source, (setter)node1_set_source_attr, "The upstream video source." },
     { "taps", (getter)blur_get_taps, (setter)blur_set_taps, "The tap list of the blur's two passes (tuple of floats; centre ntaps // 2)." },
-    { "amount", (getter)unsharp_get_amount, (setter)unsharp_set_amount, "Strength of the mask (number or frame function)." },
-    { "threshold", (getter)unsharp_get_threshold, (setter)unsharp_set_threshold, "Differences smaller than this are left alone (number or frame function)." },
+    { "amount", (getter)node1_get_scalar, (setter)unsharp_set_holder, "Strength of the mask (number or frame function).", NODE1_HOLDER(py_blur, amount) },
+    { "threshold", (getter)node1_get_scalar, (setter)unsharp_set_holder, "Differences smaller than this are left alone (number or frame function).", NODE1_HOLDER(py_blur, threshold) },
     { NULL }
 };
 static PyTypeObject py_type_Blur = {

@@ -81,26 +81,11 @@ static void adeint_render_from(py_adeint *self, int out_index, int source_frame,
 }
 
 /* closure: the holder's offset in py_adeint */
-static FrameFunctionHolder *holder_at(py_adeint *self, void *closure) { return (FrameFunctionHolder *)((char *)self + (size_t)closure); }
-static PyObject *adeint_get_scalar(py_adeint *self, void *closure) {
-    FrameFunctionHolder *h = holder_at(self, closure);
-    if (h->source) { Py_INCREF(h->source); return h->source; }
-    return PyFloat_FromDouble(h->constant[0]);
-}
 static int adeint_set_holder(py_adeint *self, PyObject *v, void *closure) {
     if (!v || v == Py_None) { PyErr_SetString(PyExc_TypeError, "the attribute takes a number or a frame function"); return -1; }
-    /* a value that is refused leaves the old one: try it on a holder of its own first */
-    FrameFunctionHolder fresh;
-    framefunc_init(&fresh, 0, 0, 0, 0);
-    if (!py_framefunc_take_source(v, &fresh)) return -1;
-    py_wrlock_nogil(&self->n.lock);
-    FrameFunctionHolder *h = holder_at(self, closure), old = *h;
-    *h = fresh;
-    pthread_rwlock_unlock(&self->n.lock);
-    py_framefunc_take_source(NULL, &old);
-    return 0;
+    return node1_set_holder(&self->n, NODE1_HOLDER_AT(self, closure), v);
 }
-#define ADEINT_HOLDER(member) ((void *)offsetof(py_adeint, member))
+#define ADEINT_HOLDER(member) NODE1_HOLDER(py_adeint, member)
 
 #define ADEINT_TYPE(P, NAME, ARGNAME, DOC)                                                                                         \
     DEFINE_NODE_VTABLE(P, CVS_FORMAT_F16, 1, 0)                                                                                    \
@@ -108,9 +93,9 @@ static int adeint_set_holder(py_adeint *self, PyObject *v, void *closure) {
     static PyGetSetDef P##_getset[] = {                                                                                            \
         { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &P##_capsule },                       \
         { "source", (getter)node1_get_source, (setter)node1_set_source_attr, "The upstream video source." },                       \
-        { "threshold", (getter)adeint_get_scalar, (setter)adeint_set_holder,                                                       \
+        { "threshold", (getter)node1_get_scalar, (setter)adeint_set_holder,                                                       \
           "Largest difference to the neighbouring frames that still counts as nothing moved (number or frame function).", ADEINT_HOLDER(threshold) }, \
-        { "softness", (getter)adeint_get_scalar, (setter)adeint_set_holder,                                                        \
+        { "softness", (getter)node1_get_scalar, (setter)adeint_set_holder,                                                        \
           "Width of the ramp from kept to interpolated rows beyond threshold; 0: a hard switch (number or frame function).", ADEINT_HOLDER(softness) }, \
         { NULL } };                                                                                                                \
     static PyMemberDef P##_members[] = { { ARGNAME, T_INT, offsetof(py_adeint, arg), READONLY, DOC }, { NULL } };                  \

@@ -12,6 +12,7 @@
 #define PY_SSIZE_T_CLEAN
 #include "pyframework.h"
 #include "canvas_scope.h"
+#include "canvas_perspective.h"
 #include <pthread.h>
 
 /* Node locks and the GIL.  Worker threads (pull queue, playback) hold the reader side of a node's rwlock across a pull,
@@ -61,14 +62,54 @@ PyObject *node1_get_source(node1 *self, void *closure);
 PyObject *node1_set_source(node1 *self, PyObject *args);
 int node1_set_source_attr(node1 *self, PyObject *value, void *closure);
 extern PyMethodDef node1_methods[];
+/* a "number or frame function" attribute of such a node: `value` is parsed into a holder of its own with no lock held (a value
+ * that is refused leaves the old one, and parsing may run Python code), swapped in under the writer lock, and what the
+ * attribute held is released after unlocking.  None and NULL give the constant 0, as py_framefunc_take_source does: a node
+ * that refuses them says so before it calls.  0, or -1 with a Python error set */
+int node1_set_holder(node1 *self, FrameFunctionHolder *holder, PyObject *value);
+PyObject *node1_get_scalar(node1 *self, void *holder_offset);       /* getter: the frame function, or the constant as a float */
+#define NODE1_HOLDER(type, member) ((void *)offsetof(type, member))
+#define NODE1_HOLDER_AT(self, offset) ((FrameFunctionHolder *)((char *)(self) + (size_t)(offset)))
 
 /* a source that fills the f16 host slot only is half-native: its f32 pull is "pull f16, widen" (main.c:105-144) */
 static inline bool half_native(const video_source *src) { return src && src->funcs && src->funcs->get_frame && !src->funcs->get_frame_32; }
+/* the device slot of a node1 whose own format is f32 and whose render takes either: an f16 pull over a half-native source is
+ * rendered as f16 directly (the entry widens, works and truncates in one launch), any other goes through the f32 render */
+void node1_get_frame_dev_half_direct(PyObject *self, int frame_index, rgba_frame_dev *frame, node_render_func render);
 
-/* shared by the geometry nodes (pytransform.c): "nearest" / "bilinear" -> CVS_TRANSFORM_*, or -1 with a Python error set;
- * transparent black over a box of `f`, its window left alone: 0, or -1 */
-int py_transform_filter_from(PyObject *v);
-int py_clear_box(rgba_frame_dev *f, int x0, int y0, int x1, int y1);
+/* the geometry nodes' shared core (pywarp.c; pytransform.c and pyperspective.c keep what differs).  A node is a table of parts
+ * -- each a constant of its shape or a frame function -- and a filter; a pull is warp_render over the node's warp_ops. */
+enum { WARP_BOX2I, WARP_PAIR, WARP_NUMBER };
+enum { WARP_PARTS = 5 };
+typedef struct { const char *name; int shape; } warp_part;
+/* given[k]: the constant as it was handed over (what the attribute reads back), NULL where the holder has a frame function */
+typedef struct { node1 n; const warp_part *table; FrameFunctionHolder part[WARP_PARTS]; PyObject *given[WARP_PARTS]; int filter; } warp_node;
+/* what a node's `plan` works out of one frame under the reader lock: the coefficients the entry takes; `need`, the source
+ * window the taps of the frame asked for can touch; `rect`, what may be pulled of it; `layer`, the window the node reports;
+ * sound: there is a map at all; refused: need clipped to rect is a window the entry will refuse (it is not pulled, the entry
+ * is still called, for its message) */
+typedef struct {
+    union { cvs_transform affine; cvs_perspective pin; } c;
+    box2i need, rect, layer;
+    bool sound, refused;
+} warp_plan;
+typedef struct {
+    void (*plan)(warp_node *self, int frame_index, const box2i *full, warp_plan *p);
+    int (*entry)(int format, void *out, const void *in, const warp_plan *p, void *stream);    /* rgba_frame_f16 or _f32, by format */
+    int (*fill_layer)(rgba_frame_dev *f, const box2i *layer);                                  /* the node's window rule */
+} warp_ops;
+void warp_node_init(warp_node *self, const warp_part *table);
+void warp_node_dealloc(warp_node *self);
+/* parts first .. first + count - 1 from values[]: all of them or, with a Python error set, none; locked: the node is alive */
+int warp_parts_set(warp_node *self, int first, int count, PyObject **values, bool locked);
+PyObject *warp_get_part(warp_node *self, void *index);              /* getter and setter of one part, closure: its index */
+int warp_set_part(warp_node *self, PyObject *value, void *index);
+PyObject *warp_get_filter(warp_node *self, void *closure);
+int warp_set_filter(warp_node *self, PyObject *value, void *closure);
+int warp_filter_from(PyObject *v);                                  /* "nearest" / "bilinear" -> CVS_TRANSFORM_*, or -1 with a Python error set */
+void warp_render(warp_node *self, int frame_index, rgba_frame_dev *f, const warp_ops *ops);
+/* transparent black over `all` minus `win` (win inside all, or empty) in at most four strips, windows left alone: 0, or -1 */
+int warp_clear_around(rgba_frame_dev *f, const box2i *all, const box2i *win);
 
 /* frame objects (pyframes.c) */
 PyObject *py_RgbaFrameF16_new(box2i *full_window, rgba_frame_f16 **frame);
@@ -110,6 +151,14 @@ int init_workspace(PyObject *module);
         .flags = VIDEO_SOURCE_FLAG_DEVICE,                                                                    \
         .get_frame = (HOST16) ? (video_get_frame_func)P##_slot_16 : NULL,                                     \
         .get_frame_32 = (HOST32) ? (video_get_frame_32_func)P##_slot_32 : NULL,                               \
+        .get_frame_dev = (video_get_frame_dev_func)P##_slot_dev };                                            \
+    static PyObject *P##_capsule;
+/* the same for a node1 with node1_get_frame_dev_half_direct in the device slot: DEFINE_NODE_VTABLE_HALF_DIRECT(Prefix) */
+#define DEFINE_NODE_VTABLE_HALF_DIRECT(P)                                                                      \
+    static void P##_slot_dev(PyObject *self, int i, rgba_frame_dev *f) { node1_get_frame_dev_half_direct(self, i, f, P##_render); } \
+    static void P##_slot_32(PyObject *self, int i, rgba_frame_f32 *f) { node_get_frame_host32(self, i, f, CVS_FORMAT_F32, P##_render); } \
+    static video_frame_source_funcs P##_funcs = {                                                             \
+        .flags = VIDEO_SOURCE_FLAG_DEVICE, .get_frame_32 = (video_get_frame_32_func)P##_slot_32,              \
         .get_frame_dev = (video_get_frame_dev_func)P##_slot_dev };                                            \
     static PyObject *P##_capsule;
 

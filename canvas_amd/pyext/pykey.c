@@ -68,45 +68,18 @@ static void key_render(PyObject *o, int frame_index, rgba_frame_dev *f) {
     }
 }
 
-static void key_slot_dev(PyObject *o, int i, rgba_frame_dev *f) {
-    py_key *self = (py_key *)o;
-    py_rdlock(&self->n.lock);
-    const bool direct = f->format == CVS_FORMAT_F16 && half_native(self->n.source);
-    pthread_rwlock_unlock(&self->n.lock);
-    if (direct) key_render(o, i, f);                    /* widen, key, truncate: one launch */
-    else node_get_frame_dev(o, i, f, CVS_FORMAT_F32, key_render);
-}
-static void key_slot_32(PyObject *o, int i, rgba_frame_f32 *f) { node_get_frame_host32(o, i, f, CVS_FORMAT_F32, key_render); }
-static video_frame_source_funcs key_funcs = {
-    .flags = VIDEO_SOURCE_FLAG_DEVICE, .get_frame_32 = (video_get_frame_32_func)key_slot_32,
-    .get_frame_dev = (video_get_frame_dev_func)key_slot_dev };
-static PyObject *key_capsule;
+DEFINE_NODE_VTABLE_HALF_DIRECT(key)                   /* widen, key, truncate: one launch */
 
-/* closure: the holder's offset in py_key */
-static FrameFunctionHolder *holder_at(py_key *self, void *closure) { return (FrameFunctionHolder *)((char *)self + (size_t)closure); }
-static PyObject *key_get_scalar(py_key *self, void *closure) {
-    FrameFunctionHolder *h = holder_at(self, closure);
-    if (h->source) { Py_INCREF(h->source); return h->source; }
-    return PyFloat_FromDouble(h->constant[0]);
-}
 static PyObject *key_get_key(py_key *self, void *closure) {
     FrameFunctionHolder *h = &self->key;
     if (h->source) { Py_INCREF(h->source); return h->source; }
     rgba_f32 color = { (float)h->constant[0], (float)h->constant[1], (float)h->constant[2], (float)h->constant[3] };
     return py_make_rgba_f32(&color);
 }
+/* closure: the holder's offset in py_key */
 static int key_set_holder(py_key *self, PyObject *v, void *closure) {
     if (!v || v == Py_None) { PyErr_SetString(PyExc_TypeError, "the attribute takes a value or a frame function"); return -1; }
-    /* a value that is refused leaves the old one: try it on a holder of its own first */
-    FrameFunctionHolder fresh;
-    framefunc_init(&fresh, 0, 0, 0, 0);
-    if (!py_framefunc_take_source(v, &fresh)) return -1;
-    py_wrlock_nogil(&self->n.lock);
-    FrameFunctionHolder *h = holder_at(self, closure), old = *h;
-    *h = fresh;
-    pthread_rwlock_unlock(&self->n.lock);
-    py_framefunc_take_source(NULL, &old);
-    return 0;
+    return node1_set_holder(&self->n, NODE1_HOLDER_AT(self, closure), v);
 }
 static PyObject *key_get_matte(py_key *self, void *closure) { return PyBool_FromLong(self->show_matte); }
 static int key_set_matte(py_key *self, PyObject *v, void *closure) {
@@ -117,15 +90,15 @@ static int key_set_matte(py_key *self, PyObject *v, void *closure) {
     return 0;
 }
 
-#define KEY_HOLDER(member) ((void *)offsetof(py_key, member))
+#define KEY_HOLDER(member) NODE1_HOLDER(py_key, member)
 static PyGetSetDef key_getset[] = {
     { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &key_capsule },
     { "source", (getter)node1_get_source, (setter)node1_set_source_attr, "The upstream video source." },
     { "key", (getter)key_get_key, (setter)key_set_holder, "The colour to remove (rgba or frame function; alpha ignored).", KEY_HOLDER(key) },
-    { "tolerance", (getter)key_get_scalar, (setter)key_set_holder, "Chroma distance up to which a pixel is removed entirely (number or frame function).", KEY_HOLDER(tolerance) },
-    { "softness", (getter)key_get_scalar, (setter)key_set_holder, "Width of the ramp from removed to kept beyond tolerance; 0: a hard edge (number or frame function).", KEY_HOLDER(softness) },
-    { "spill", (getter)key_get_scalar, (setter)key_set_holder, "Strength of the spill suppression, 0..1 (number or frame function).", KEY_HOLDER(spill) },
-    { "spill_range", (getter)key_get_scalar, (setter)key_set_holder, "Distance beyond tolerance over which the suppression fades to none (number or frame function).", KEY_HOLDER(spill_range) },
+    { "tolerance", (getter)node1_get_scalar, (setter)key_set_holder, "Chroma distance up to which a pixel is removed entirely (number or frame function).", KEY_HOLDER(tolerance) },
+    { "softness", (getter)node1_get_scalar, (setter)key_set_holder, "Width of the ramp from removed to kept beyond tolerance; 0: a hard edge (number or frame function).", KEY_HOLDER(softness) },
+    { "spill", (getter)node1_get_scalar, (setter)key_set_holder, "Strength of the spill suppression, 0..1 (number or frame function).", KEY_HOLDER(spill) },
+    { "spill_range", (getter)node1_get_scalar, (setter)key_set_holder, "Distance beyond tolerance over which the suppression fades to none (number or frame function).", KEY_HOLDER(spill_range) },
     { "show_matte", (getter)key_get_matte, (setter)key_set_matte, "Show (a', a', a', 1) instead of the keyed picture." },
     { NULL }
 };

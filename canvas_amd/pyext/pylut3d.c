@@ -197,19 +197,7 @@ static void lutnode_render(PyObject *o, int frame_index, rgba_frame_dev *f) {
     pthread_rwlock_unlock(&self->n.lock);               /* only now: the launch that reads the copy is queued */
 }
 
-static void lutnode_slot_dev(PyObject *o, int i, rgba_frame_dev *f) {
-    py_lut_node *self = (py_lut_node *)o;
-    py_rdlock(&self->n.lock);
-    const bool direct = f->format == CVS_FORMAT_F16 && half_native(self->n.source);
-    pthread_rwlock_unlock(&self->n.lock);
-    if (direct) lutnode_render(o, i, f);                /* widen, look up, truncate: one launch */
-    else node_get_frame_dev(o, i, f, CVS_FORMAT_F32, lutnode_render);
-}
-static void lutnode_slot_32(PyObject *o, int i, rgba_frame_f32 *f) { node_get_frame_host32(o, i, f, CVS_FORMAT_F32, lutnode_render); }
-static video_frame_source_funcs lutnode_funcs = {
-    .flags = VIDEO_SOURCE_FLAG_DEVICE, .get_frame_32 = (video_get_frame_32_func)lutnode_slot_32,
-    .get_frame_dev = (video_get_frame_dev_func)lutnode_slot_dev };
-static PyObject *lutnode_capsule;
+DEFINE_NODE_VTABLE_HALF_DIRECT(lutnode)               /* widen, look up, truncate: one launch */
 
 static PyObject *lutnode_get_lut(py_lut_node *self, void *closure) { Py_INCREF(self->lut); return (PyObject *)self->lut; }
 static int lutnode_set_lut(py_lut_node *self, PyObject *v, void *closure) {

@@ -115,40 +115,16 @@ static void matte_render(PyObject *o, int frame_index, rgba_frame_dev *f) {
     if (in.data) cvs_pool_free(in.data, f->stream);
 }
 
-static void matte_slot_dev(PyObject *o, int i, rgba_frame_dev *f) {
-    py_matte *self = (py_matte *)o;
-    py_rdlock(&self->n.lock);
-    const bool direct = f->format == CVS_FORMAT_F16 && half_native(self->n.source);
-    pthread_rwlock_unlock(&self->n.lock);
-    if (direct) matte_render(o, i, f);                  /* widen, every stage, truncate: one launch */
-    else node_get_frame_dev(o, i, f, CVS_FORMAT_F32, matte_render);
-}
-static void matte_slot_32(PyObject *o, int i, rgba_frame_f32 *f) { node_get_frame_host32(o, i, f, CVS_FORMAT_F32, matte_render); }
-static video_frame_source_funcs matte_funcs = {
-    .flags = VIDEO_SOURCE_FLAG_DEVICE, .get_frame_32 = (video_get_frame_32_func)matte_slot_32,
-    .get_frame_dev = (video_get_frame_dev_func)matte_slot_dev };
-static PyObject *matte_capsule;
+DEFINE_NODE_VTABLE_HALF_DIRECT(matte)                 /* widen, every stage, truncate: one launch */
 
-/* closure: the holder's offset in py_matte */
-static FrameFunctionHolder *holder_at(py_matte *self, void *closure) { return (FrameFunctionHolder *)((char *)self + (size_t)closure); }
-static PyObject *matte_get_scalar(py_matte *self, void *closure) {
-    FrameFunctionHolder *h = holder_at(self, closure);
-    if (h->source) { Py_INCREF(h->source); return h->source; }
-    if (h == &self->choke) return PyLong_FromLong(lround(h->constant[0]));
-    return PyFloat_FromDouble(h->constant[0]);
+static PyObject *matte_get_choke(py_matte *self, void *closure) {       /* a count of pixels: read back as an int */
+    if (self->choke.source) { Py_INCREF(self->choke.source); return self->choke.source; }
+    return PyLong_FromLong(lround(self->choke.constant[0]));
 }
+/* closure: the holder's offset in py_matte */
 static int matte_set_holder(py_matte *self, PyObject *v, void *closure) {
     if (!v || v == Py_None) { PyErr_SetString(PyExc_TypeError, "the attribute takes a value or a frame function"); return -1; }
-    /* a value that is refused leaves the old one: try it on a holder of its own first */
-    FrameFunctionHolder fresh;
-    framefunc_init(&fresh, 0, 0, 0, 0);
-    if (!py_framefunc_take_source(v, &fresh)) return -1;
-    py_wrlock_nogil(&self->n.lock);
-    FrameFunctionHolder *h = holder_at(self, closure), old = *h;
-    *h = fresh;
-    pthread_rwlock_unlock(&self->n.lock);
-    py_framefunc_take_source(NULL, &old);
-    return 0;
+    return node1_set_holder(&self->n, NODE1_HOLDER_AT(self, closure), v);
 }
 static PyObject *matte_get_feather(py_matte *self, void *closure) {
     py_rdlock(&self->n.lock);
@@ -185,14 +161,14 @@ static int matte_set_show(py_matte *self, PyObject *v, void *closure) {
     return 0;
 }
 
-#define MATTE_HOLDER(member) ((void *)offsetof(py_matte, member))
+#define MATTE_HOLDER(member) NODE1_HOLDER(py_matte, member)
 static PyGetSetDef matte_getset[] = {
     { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &matte_capsule },
     { "source", (getter)node1_get_source, (setter)node1_set_source_attr, "The upstream video source." },
-    { "choke", (getter)matte_get_scalar, (setter)matte_set_holder, "Pixels to shrink (> 0) or grow (< 0) the matte by, at most 16 (number or frame function).", MATTE_HOLDER(choke) },
+    { "choke", (getter)matte_get_choke, (setter)matte_set_holder, "Pixels to shrink (> 0) or grow (< 0) the matte by, at most 16 (number or frame function).", MATTE_HOLDER(choke) },
     { "feather", (getter)matte_get_feather, (setter)matte_set_feather, "The tap list that blurs the matte (an odd count of up to 25 floats, centre ntaps // 2) or None." },
-    { "black", (getter)matte_get_scalar, (setter)matte_set_holder, "Alpha at or below this becomes 0 (number or frame function).", MATTE_HOLDER(black) },
-    { "white", (getter)matte_get_scalar, (setter)matte_set_holder, "Alpha at or above this becomes 1 (number or frame function).", MATTE_HOLDER(white) },
+    { "black", (getter)node1_get_scalar, (setter)matte_set_holder, "Alpha at or below this becomes 0 (number or frame function).", MATTE_HOLDER(black) },
+    { "white", (getter)node1_get_scalar, (setter)matte_set_holder, "Alpha at or above this becomes 1 (number or frame function).", MATTE_HOLDER(white) },
     { "show_matte", (getter)matte_get_show, (setter)matte_set_show, "Show (a, a, a, 1) of the refined matte instead of the picture." },
     { NULL }
 };

@@ -148,22 +148,9 @@ static int scope_set_rect(py_scope *self, PyObject *v, void *c) {
     pthread_rwlock_unlock(&self->n.lock);
     return 0;
 }
-static PyObject *scope_get_gain(py_scope *self, void *c) {
-    if (self->gain.source) { Py_INCREF(self->gain.source); return self->gain.source; }
-    return PyFloat_FromDouble(self->gain.constant[0]);
-}
 static int scope_set_gain(py_scope *self, PyObject *v, void *c) {
     if (!v || v == Py_None) { PyErr_SetString(PyExc_TypeError, "gain takes a number or a frame function"); return -1; }
-    /* a value that is refused leaves the old one: try it on a holder of its own first */
-    FrameFunctionHolder fresh;
-    framefunc_init(&fresh, 0, 0, 0, 0);
-    if (!py_framefunc_take_source(v, &fresh)) return -1;
-    py_wrlock_nogil(&self->n.lock);
-    FrameFunctionHolder old = self->gain;
-    self->gain = fresh;
-    pthread_rwlock_unlock(&self->n.lock);
-    py_framefunc_take_source(NULL, &old);
-    return 0;
+    return node1_set_holder(&self->n, &self->gain, v);
 }
 static PyObject *scope_get_skip(py_scope *self, void *c) { return PyBool_FromLong(self->skip); }
 static int scope_set_skip(py_scope *self, PyObject *v, void *c) {
@@ -181,7 +168,7 @@ static PyGetSetDef scope_getset[] = {
     { "source_rect", (getter)scope_get_rect, (setter)scope_set_rect, "The part of the source that is measured (box2i)." },
     { "columns", (getter)scope_get_columns, (setter)scope_set_columns, "Output columns of a waveform, of each panel of a parade." },
     { "display", (getter)scope_get_display, (setter)scope_set_display, "\"export\" (the exporter's bytes) or \"widget\" (the software widget's)." },
-    { "gain", (getter)scope_get_gain, (setter)scope_set_gain, "Brightness per counted pixel (number or frame function)." },
+    { "gain", (getter)node1_get_scalar, (setter)scope_set_gain, "Brightness per counted pixel (number or frame function).", NODE1_HOLDER(py_scope, gain) },
     { "skip_transparent", (getter)scope_get_skip, (setter)scope_set_skip, "Leave out the pixels whose alpha byte is 0." },
     { NULL }
 };

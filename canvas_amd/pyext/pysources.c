@@ -113,6 +113,30 @@ int node1_set_source_attr(node1 *self, PyObject *value, void *c) {
     pthread_rwlock_unlock(&self->lock);
     return ok ? 0 : -1;
 }
+int node1_set_holder(node1 *self, FrameFunctionHolder *h, PyObject *v) {
+    FrameFunctionHolder fresh;
+    framefunc_init(&fresh, 0, 0, 0, 0);
+    if (!py_framefunc_take_source(v, &fresh)) return -1;
+    py_wrlock_nogil(&self->lock);
+    FrameFunctionHolder old = *h;
+    *h = fresh;
+    pthread_rwlock_unlock(&self->lock);
+    py_framefunc_take_source(NULL, &old);
+    return 0;
+}
+PyObject *node1_get_scalar(node1 *self, void *holder_offset) {
+    FrameFunctionHolder *h = NODE1_HOLDER_AT(self, holder_offset);
+    if (h->source) { Py_INCREF(h->source); return h->source; }
+    return PyFloat_FromDouble(h->constant[0]);
+}
+void node1_get_frame_dev_half_direct(PyObject *o, int frame_index, rgba_frame_dev *f, node_render_func render) {
+    node1 *self = (node1 *)o;
+    py_rdlock(&self->lock);
+    const bool direct = f->format == CVS_FORMAT_F16 && half_native(self->source);
+    pthread_rwlock_unlock(&self->lock);
+    if (direct) render(o, frame_index, f);
+    else node_get_frame_dev(o, frame_index, f, CVS_FORMAT_F32, render);
+}
 
 /* ---------------------------------------------------------------- VideoGainOffsetFilter */
 
@@ -152,19 +176,13 @@ static void gain_render(PyObject *o, int frame_index, rgba_frame_dev *f) {      
 }
 DEFINE_NODE_VTABLE(gain, CVS_FORMAT_F16, 1, 0)
 static void *gain_unused[] UNUSED = { (void *)gain_slot_32 };
-static PyObject *holder_get(FrameFunctionHolder *h) {
-    if (h->source) { Py_INCREF(h->source); return h->source; }
-    return PyFloat_FromDouble(h->constant[0]);
-}
-static PyObject *gain_get_gain(py_gain *self, void *c) { return holder_get(&self->gain); }
-static PyObject *gain_get_offset(py_gain *self, void *c) { return holder_get(&self->offset); }
-static int gain_set_gain(py_gain *self, PyObject *v, void *c) { return py_framefunc_take_source(v, &self->gain) ? 0 : -1; }
-static int gain_set_offset(py_gain *self, PyObject *v, void *c) { return py_framefunc_take_source(v, &self->offset) ? 0 : -1; }
+/* None is taken as 0, as the reference takes it (VideoGainOffsetFilter.c:174-187, whose setters hold the writer lock too) */
+static int gain_set_holder(py_gain *self, PyObject *v, void *offset) { return node1_set_holder(&self->n, NODE1_HOLDER_AT(self, offset), v); }
 static PyGetSetDef gain_getset[] = {
     { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &gain_capsule },
     { "source", (getter)node1_get_source, (setter)node1_set_source_attr, "The upstream video source." },
-    { "gain", (getter)gain_get_gain, (setter)gain_set_gain, "Gain (number or frame function)." },
-    { "offset", (getter)gain_get_offset, (setter)gain_set_offset, "Offset (number or frame function)." },
+    { "gain", (getter)node1_get_scalar, (setter)gain_set_holder, "Gain (number or frame function).", NODE1_HOLDER(py_gain, gain) },
+    { "offset", (getter)node1_get_scalar, (setter)gain_set_holder, "Offset (number or frame function).", NODE1_HOLDER(py_gain, offset) },
     { NULL }
 };
 PyMethodDef node1_methods[] = {

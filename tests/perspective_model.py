@@ -16,7 +16,6 @@ import math
 import numpy as np
 
 from tests import transform_model as tm
-from tests.models import f2h_rz_model
 from tests.unsharp_model import crop, intersect, widen  # noqa: F401  (re-exported for the tests)
 
 F32 = np.float32
@@ -163,47 +162,9 @@ def perspective_plane(source, S, p, filt, window):
     _h, _to, so = p
     rel = (S[0] - so[0], S[1] - so[1], S[2] - so[0], S[3] - so[1])
     u, v, w = source_coords(p, window)
-    out = _sample(source, rel, u, v, filt)
+    out = tm.sample(source, rel, u, v, filt)
     with np.errstate(invalid="ignore"):
         out[~(w > 0)] = 0
-    return out
-
-
-def _sample(source, S, u, v, filt):
-    """tests/transform_model.py transform_plane from u, v on: S and u, v in one coordinate system"""
-    half = source.dtype == np.uint16
-    wide = widen(source) if half else np.ascontiguousarray(source, F32)
-    out = np.zeros(u.shape + (4,), source.dtype)
-    inside, fetch = tm.inside, tm._fetch
-    with np.errstate(all="ignore"):
-        if filt == NEAREST:
-            i, j = np.floor((u + F32(0.5)).astype(F32)), np.floor((v + F32(0.5)).astype(F32))
-            ok = inside(i, j, S)
-            out[ok] = fetch(source, S, i, j, ok)[ok]
-            return out
-        i, j = np.floor(u), np.floor(v)
-        a, b = (u - i).astype(F32), (v - j).astype(F32)
-        wa, wb = (F32(1) - a).astype(F32), (F32(1) - b).astype(F32)
-        A = np.zeros(u.shape, F32)
-        C = [np.zeros(u.shape, F32) for _ in range(3)]
-        for wt, di, dj in (((wa * wb).astype(F32), 0, 0), ((a * wb).astype(F32), 1, 0), ((wa * b).astype(F32), 0, 1), ((a * b).astype(F32), 1, 1)):
-            ti, tj = (i + F32(di)).astype(F32), (j + F32(dj)).astype(F32)
-            ok = inside(ti, tj, S)
-            px = fetch(wide, S, ti, tj, ok)
-            q = (wt * px[..., 3]).astype(F32)
-            A = np.where(ok, (A + q).astype(F32), A)
-            for ch in range(3):
-                C[ch] = np.where(ok, (C[ch] + (q * px[..., ch]).astype(F32)).astype(F32), C[ch])
-        solid = A != 0
-        result = np.zeros(u.shape + (4,), F32)
-        for ch in range(3):
-            result[..., ch] = np.where(solid, (C[ch] / A).astype(F32), F32(0))
-        result[..., 3] = np.where(solid, A, F32(0))
-        out[...] = f2h_rz_model(result) if half else result
-        on_sample = (a == 0) & (b == 0)
-        ok = inside(i, j, S)
-        copied = np.where(ok[..., None], fetch(source, S, i, j, ok), np.zeros(4, source.dtype))
-        out[on_sample] = copied[on_sample]
     return out
 
 

@@ -221,6 +221,47 @@ def test_frame_func_pass_through_filter(process):
     assert Shifted(inner, 1.0).get_values(0) == inner.get_values(1.0)
 
 
+def _holder_attributes(process):
+    """(node, attribute, a number it takes) of every "number or frame function" attribute that is set through the one swap of
+    pysources.c (node1_set_holder)"""
+    red = process.SolidColorVideoSource((1, 0, 0, 1))
+    box = ((0, 0), (15, 15))
+    nodes = [(process.VideoGainOffsetFilter(red), ("gain", "offset")),
+             (process.VideoUnsharpMaskFilter(red, (0.25, 0.5, 0.25)), ("amount", "threshold")),
+             (process.VideoChromaKeyFilter(red, (0, 1, 0, 1)), ("tolerance", "softness", "spill", "spill_range")),
+             (process.VideoMatteFilter(red), ("choke", "black", "white")),
+             (process.AdaptiveDeinterlaceFilter(red), ("threshold", "softness")),
+             (process.AdaptiveBobDeinterlaceFilter(red), ("threshold", "softness")),
+             (process.VideoScopeFilter(red, "waveform", box), ("gain",))]
+    return [(node, name, 2 if name == "choke" else 0.375) for node, names in nodes for name in names]
+
+
+def test_holder_attributes_swap_whole_or_not_at_all(process):
+    """A number reads back, a frame function reads back as itself, and a value that is refused leaves the frame function in
+    place (it is parsed into a holder of its own before anything is swapped).  None is refused like any other wrong value,
+    except by VideoGainOffsetFilter, which takes it as 0 as the reference does."""
+    cases = _holder_attributes(process)
+    assert len(cases) == 2 + 2 + 4 + 3 + 2 + 2 + 1
+    for node, name, number in cases:
+        where = (type(node).__name__, name)
+        setattr(node, name, number)
+        assert getattr(node, name) == number and type(getattr(node, name)) is type(number), where
+        ramp = process.LerpFunc((0.0,), (1.0,), 5.0)
+        setattr(node, name, ramp)
+        assert getattr(node, name) is ramp, where
+        for bad in ("much", object()):
+            with pytest.raises(Exception):
+                setattr(node, name, bad)
+            assert getattr(node, name) is ramp, where
+        if isinstance(node, process.VideoGainOffsetFilter):
+            setattr(node, name, None)
+            assert getattr(node, name) == 0.0, where
+        else:
+            with pytest.raises(TypeError):
+                setattr(node, name, None)
+            assert getattr(node, name) is ramp, where
+
+
 def test_pulldown_cadence_table(process):
     """Pulldown23RemovalFilter.c:51-71.  The comment table there lists, per cadence offset, which source frame each of
     the four output frames of a cycle comes from; offsets 0-3 follow it.  For offset 4 the CODE sends the whole-frame

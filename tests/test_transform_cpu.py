@@ -454,6 +454,24 @@ def test_model_transparent_neighbourhoods_give_zeros():
         assert np.array_equal(_bits(near), np.rot90(_bits(pixels), -1))   # nearest copies the hole, colour and all
 
 
+def test_model_sampler_is_the_one_both_warps_share():
+    """transform_plane is sample() over its own coordinates, and the corner pin's plane with affine coefficients and zero origins
+    is the same bytes: the model-side twin of test_affine_coefficients_with_zero_origins_give_the_transforms_bytes."""
+    from tests import perspective_model as pm
+    rng = np.random.default_rng(11)
+    source = rng.uniform(0.0, 1.0, (7, 9, 4)).astype(np.float32)
+    source[2:4, 3:6, 3] = 0.0
+    S, win = (0, 0, 8, 6), (-2, -1, 9, 8)                            # 9 x 7 under a 12 x 10 window: taps outside S on every side
+    m = tm.from_parts(anchor=(4.0, 3.0), rotation=30.0, position=(4.0, 3.0))
+    p = (tuple(m) + (0.0, 0.0, 1.0), (0, 0), (0, 0))
+    for pixels in (f2h_rz_model(source), source):
+        for filt in FILTERS:
+            plane = tm.transform_plane(pixels, S, m, filt, win)
+            assert plane.dtype == pixels.dtype and plane.shape == (10, 12, 4) and plane.any() and not plane[0, 0].any()
+            assert plane.tobytes() == tm.sample(pixels, S, *tm.source_coords(m, win), filt).tobytes()
+            assert plane.tobytes() == pm.perspective_plane(pixels, S, p, filt, win).tobytes()
+
+
 # ---------------------------------------------------------------- the code object
 
 def test_code_object_holds_every_instance_without_scratch():

@@ -110,6 +110,7 @@ def test_unsharp_arguments(process):
     assert node.amount == 1.5
     with pytest.raises(Exception):
         node.amount = "much"
+    assert node.amount == 1.5
     with pytest.raises(TypeError):
         process.VideoBlurFilter(red, TAPS, 1.0)                    # the blur has neither
     assert not hasattr(process.VideoBlurFilter(red, TAPS), "amount")

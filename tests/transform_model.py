@@ -125,9 +125,14 @@ def _fetch(src, S, i, j, ok):
 
 def transform_plane(source, S, m, filt, window):
     """The infinite-plane result over target window `window`.  source: pixels over S (uint16 codes or float32) -> same format."""
+    return sample(source, S, *source_coords(m, window), filt)
+
+
+def sample(source, S, u, v, filt):
+    """The filter from the source coordinates on, shared with tests/perspective_model.py: S and the float32 planes u, v in one
+    coordinate system, source the pixels over S."""
     half = source.dtype == np.uint16
     wide = widen(source) if half else np.ascontiguousarray(source, F32)
-    u, v = source_coords(m, window)
     out = np.zeros(u.shape + (4,), source.dtype)
     with np.errstate(all="ignore"):
         if filt == NEAREST:
