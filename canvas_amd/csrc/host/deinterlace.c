@@ -17,16 +17,20 @@ static bool present(const rgba_frame_f16 *f) { return f && !box2i_is_empty(&f->c
 
 CVS_EXPORT int cvs_deinterlace_adaptive_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *prev, const rgba_frame_f16 *cur,
                                                 const rgba_frame_f16 *next, const cvs_deinterlace_adaptive *p, cvs_stream_t s) {
+    /* Asked before the output's window is emptied: handed in as ONE struct, the output is that input, window and all, and a
+     * neighbour would then pass for absent (canvas_hip.h "Operands that share a buffer"). */
+    const rgba_frame_f16 *in[3] = { cur, prev, next };
+    bool shares = false;
+    for (int i = 0; out && i < 3; i++) shares = shares || (in[i] && (i == 0 || present(in[i])) && out->data == in[i]->data);
     if (out) box2i_set_empty(&out->current_window);
     if (!out || !cur || !p) { cvs_set_error("%s: need the frames and the parameters", what); return -1; }
     if (p->field != 0 && p->field != 1) { cvs_set_error("%s: field %d is neither 0 (even rows) nor 1 (odd rows)", what, p->field); return -1; }
     if (p->flags != 0) { cvs_set_error("%s: unknown flags 0x%x", what, (unsigned)p->flags); return -1; }
     if (!isfinite(p->threshold)) { cvs_set_error("%s: threshold %g must be finite", what, p->threshold); return -1; }
     if (!isfinite(p->softness) || p->softness < 0.0f) { cvs_set_error("%s: softness %g must be finite and not negative", what, p->softness); return -1; }
-    const rgba_frame_f16 *in[3] = { cur, prev, next };
+    if (shares) { cvs_set_error("%s: the output cannot be one of the inputs", what); return -1; }
     for (int i = 0; i < 3; i++) {
         if (!in[i]) continue;
-        if ((i == 0 || present(in[i])) && out->data == in[i]->data) { cvs_set_error("%s: the output cannot be one of the inputs", what); return -1; }
         if (!cvs_box_contains(&in[i]->full_window, &in[i]->current_window)) { cvs_set_error("%s: an input's current_window lies outside its buffer", what); return -1; }
     }
     if (cvs_coords_refused(what, "out", &out->full_window, NULL, CVS_MAX_COORD)) return -1;

@@ -48,6 +48,12 @@ CVS_EXPORT int cvs_pulldown23_frames(int offset, int frame_index, int *first, in
 
 /* :88-104: `other` was pulled into a buffer allocated for frame->current_window; its even rows replace the frame's */
 CVS_EXPORT int cvs_weave_fields_f16_dev(rgba_frame_f16 *frame, const rgba_frame_f16 *other, cvs_stream_t s) {
+    /* the second field's row address is the reference's, columns counted from x = 0: a lane reads a pixel another lane writes */
+    if (frame->data && frame->data == other->data) {
+        cvs_set_error("cvs_weave_fields_f16_dev: the output cannot be one of the inputs");
+        box2i_set_empty(&frame->current_window);
+        return -1;
+    }
     if (cvs_enter() != 0) return -1;
     CVS_REQUIRE_COORDS(frame, 1, frame, "cvs_weave_fields_f16_dev", "frame");
     if (cvs_coords_refused("cvs_weave_fields_f16_dev", "other", &other->full_window, &other->current_window, CVS_MAX_COORD)) { box2i_set_empty(&frame->current_window); return -1; }

@@ -71,10 +71,20 @@ static any_frame any_of(const frame_ref *f, int half) {
 /* What a single-frame entry checks first, with its frames as frame_of() reads them into *t, *src: a device for the call,
  * and a source window inside its own buffer (else a kernel would read past it).  On refusal the target's window is
  * emptied; `what` names the entry point.  `lim`: the coordinate bound of the entry's family (CVS_MAX_COORD; the resamplers,
- * which form positions in float: CVS_RESAMPLE_MAX_COORD). */
+ * which form positions in float: CVS_RESAMPLE_MAX_COORD).
+ * First of all, before any device call: a target that is the source's buffer.  Every kernel behind these entries gathers
+ * source pixels that another lane, or another workgroup, writes as target pixels (canvas_hip.h "Operands that share a
+ * buffer"): none of them runs in place, whichever takes the call. */
+static bool shares_buffer(const frame_ref *t, const frame_ref *src, const char *what) {
+    if (!t->data || t->data != src->data) return false;
+    cvs_set_error("%s: the target is the source's buffer: the operation is not in place", what);
+    return true;
+}
+
 static bool entry_refused(void *target, const void *source, int half, const char *what, frame_ref *t, frame_ref *src, int lim) {
     *t = frame_of(target, half);
     *src = frame_of(source, half);
+    if (shares_buffer(t, src, what)) { box2i_set_empty(t->cur); return true; }
     if (cvs_enter() != 0) { box2i_set_empty(t->cur); return true; }
     if (!cvs_box_contains(src->full, src->cur)) {
         cvs_set_error("%s: the input's current_window lies outside its buffer", what);
@@ -94,7 +104,7 @@ static void batch_empty_from(const void *targets, int from, int count, int half)
 
 /* What `count` single calls would refuse, a batch entry refuses before anything is launched: null arrays or frames; a
  * source window outside its buffer (it would send a kernel's rows out of bounds) or no device, with every target's window
- * emptied. */
+ * emptied; a frame whose target is its own source's buffer, likewise, and first. */
 static bool batch_refused(const void *targets, const void *sources, int count, int half, const char *what, int lim) {
     if (!targets || !sources) { cvs_set_error("%s: bad arguments", what); return true; }
     for (int i = 0; i < count; i++)
@@ -102,6 +112,10 @@ static bool batch_refused(const void *targets, const void *sources, int count, i
             cvs_set_error("%s: frame %d of %d is a null pointer", what, i, count);
             return true;
         }
+    for (int i = 0; i < count; i++) {
+        const frame_ref t = frame_at(targets, i, half), src = frame_at(sources, i, half);
+        if (shares_buffer(&t, &src, what)) { batch_empty_from(targets, 0, count, half); return true; }
+    }
     for (int i = 0; i < count; i++) {
         const frame_ref src = frame_at(sources, i, half);
         if (!cvs_box_contains(src.full, src.cur)) {
@@ -658,7 +672,7 @@ static int fir_blur(void *target, const void *source, const float *taps, int nta
     box2i_intersect(&win, src.cur, t.full);
     *t.cur = win;
     if (box2i_is_empty(&win)) return 0;
-    const any_frame tf = any_of(&t, half), sf = any_of(&src, half);      /* (taken after the window: a blur in place reads it) */
+    const any_frame tf = any_of(&t, half), sf = any_of(&src, half);      /* (taken after the window: the kernels' target view carries none) */
     int rc = blur_fused(&tf, &sf, &win, taps, ntaps, NULL, 0, NULL, s);
     if (rc != 0) box2i_set_empty(t.cur);
     return rc;
@@ -734,6 +748,13 @@ CVS_EXPORT int cvs_unsharp_mask_f16_dev(rgba_frame_f16 *target, const rgba_frame
  * window is the whole output frame; otherwise the same nodes one by one on f32 frames. */
 CVS_EXPORT int cvs_blur_over_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *source, const float *taps, int ntaps,
                                      const rgba_frame_f16 *const *overlays, int noverlays, cvs_stream_t stream) {
+    /* out may be one of the overlays -- a lane reads an overlay's pixel where it writes, before it writes, and node by node
+     * the output is written last -- but not the source, which the blur gathers from */
+    if (out->data && out->data == source->data) {
+        cvs_set_error("cvs_blur_over_f16_dev: the target is the source's buffer: the operation is not in place");
+        box2i_set_empty(&out->current_window);
+        return -1;
+    }
     if (cvs_enter() != 0) { box2i_set_empty(&out->current_window); return -1; }
     CVS_REQUIRE_INSIDE(source, out, "cvs_blur_over_f16_dev");
     CVS_REQUIRE_COORDS(source, 1, out, "cvs_blur_over_f16_dev", "source");
@@ -809,6 +830,11 @@ CVS_EXPORT int cvs_resample_lanczos_f16_dev(rgba_frame_f16 *target, const rgba_f
  * launches with one f32 intermediate; the widen and the truncate ride on the first load and the last store. */
 CVS_EXPORT int cvs_blur_lanczos_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const float *taps, int ntaps,
                                         float fx, float fy, int ksize, cvs_stream_t stream) {
+    if (target->data && target->data == source->data) {
+        cvs_set_error("cvs_blur_lanczos_f16_dev: the target is the source's buffer: the operation is not in place");
+        box2i_set_empty(&target->current_window);
+        return -1;
+    }
     if (cvs_enter() != 0) { box2i_set_empty(&target->current_window); return -1; }
     CVS_REQUIRE_INSIDE(source, target, "cvs_blur_lanczos_f16_dev");
     if (cvs_coords_refused("cvs_blur_lanczos_f16_dev", "source", &source->full_window, &source->current_window, CVS_RESAMPLE_MAX_COORD) ||

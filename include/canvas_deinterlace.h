@@ -45,6 +45,7 @@ typedef struct cvs_deinterlace_adaptive {
     int   flags;        /* none defined: 0 */
 } cvs_deinterlace_adaptive;
 
+/* out as one of the inputs is refused, the inputs may be one buffer: canvas_hip.h "Operands that share a buffer" */
 CVS_EXPORT int cvs_deinterlace_adaptive_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *prev, const rgba_frame_f16 *cur,
                                                 const rgba_frame_f16 *next, const cvs_deinterlace_adaptive *p, cvs_stream_t s);
 

@@ -386,6 +386,51 @@ CVS_EXPORT int cvs_half_lookup_dev(const half *table_dev, half *out, const half 
 
 /* frames in HBM (frame->data is a device pointer); window logic runs on the host exactly as in
  * the reference and the structs are updated before the call returns; pixels are enqueued on `s` */
+
+/* Operands that share a buffer (DESIGN.md "Operands that share a buffer"; tests/alias_cases.py holds this block to the library).
+ * Frames are the caller's device pointers, so one buffer can be handed to a device entry twice.  Two frame operands SHARE A
+ * BUFFER when their `data` pointers are equal and their `full_window`s are equal: one struct handed in for both parameters,
+ * or two structs (whatever their `current_window`s).  For every pair of frame operands of every cvs_*_dev entry -- a frame the
+ * entry writes against one it reads, or two it reads -- exactly one of three things holds, whatever path, kernel or
+ * cvs_fir_path_override() pin takes the call; the lists name the entry and its pairs by their parameters (a table of frame
+ * pointers pairs with itself; a cvs_chain_job is its `out` and its `layers`), those of the extension headers included:
+ *   - IN PLACE: the entry computes, bit for bit, windows included, what the same call gives on a distinct copy of the input.
+ *   - REFUSED: the entry returns nonzero before any device call, table look-up or pool allocation; cvs_last_error() names the
+ *     entry and says "the target is the source's buffer: the operation is not in place" or "the output cannot be one of the
+ *     inputs"; the written frame's current_window is empty; no buffer is touched.  A batch refuses as a whole, with every
+ *     target's window empty, when any frame's target is that frame's source.
+ *   - SHARED: both operands are only read, and may be one buffer.
+ * An entry never returns 0 with pixels that differ from the out-of-place call.  Not covered, and the caller's error wherever
+ * an entry's own text does not say otherwise (the chain, the scaler batches): equal `data` under different `full_window`s,
+ * buffers that overlap at a shifted address, and two operands that are both written.
+ *   in place:
+ *     cvs_half_lookup_dev (out, in); cvs_copy_frame_f16_dev (out, in); cvs_copy_frame_alpha_f32_dev (out, in);
+ *     cvs_gain_offset_f16_dev (out, in); cvs_color_matrix_f16_to_dev (out, in);
+ *     cvs_mix_cross_f32_dev (out, a) (out, b); cvs_mix_over_f32_dev (out, b); cvs_mix_cross_f16_dev (out, a) (out, b);
+ *     cvs_chain_color_over_f16_dev (out, layers); cvs_chroma_key_f16_dev (target, source); cvs_chroma_key_f32_dev (target, source);
+ *     cvs_lut3d_f16_dev (target, source); cvs_lut3d_f32_dev (target, source);
+ *     cvs_blur_over_f16_dev (out, overlays); cvs_blur_over_f16_batch_dev (outs, overlays)
+ *   refused:
+ *     cvs_weave_fields_f16_dev (frame, other); cvs_field_to_frame_f16_dev (out, in); cvs_soften_fields_f16_dev (out, in);
+ *     cvs_interlace_fields_f16_dev (out, even) (out, odd);
+ *     cvs_matte_refine_f16_dev (target, source); cvs_matte_refine_f32_dev (target, source);
+ *     cvs_transform_f16_dev (target, source); cvs_transform_f32_dev (target, source);
+ *     cvs_perspective_f16_dev (target, source); cvs_perspective_f32_dev (target, source);
+ *     cvs_deinterlace_adaptive_f16_dev (out, prev) (out, cur) (out, next);
+ *     cvs_fir_blur_f32_dev (target, source); cvs_fir_blur_f16_dev (target, source);
+ *     cvs_unsharp_mask_f32_dev (target, source); cvs_unsharp_mask_f16_dev (target, source);
+ *     cvs_resample_lanczos_f32_dev (target, source); cvs_resample_lanczos_f16_dev (target, source);
+ *     cvs_scale_bilinear_f32_dev (target, source); cvs_scale_bilinear_f16_dev (target, source);
+ *     cvs_scale_bilinear_f32_batch_dev (targets, sources); cvs_scale_bilinear_f16_batch_dev (targets, sources);
+ *     cvs_blur_lanczos_f16_dev (target, source); cvs_blur_lanczos_f16_batch_dev (targets, sources);
+ *     cvs_blur_over_f16_dev (out, source); cvs_blur_over_f16_batch_dev (outs, sources)
+ *   shared:
+ *     cvs_mix_cross_f32_dev (a, b); cvs_mix_cross_f16_dev (a, b); cvs_chain_color_over_f16_dev (layers, layers);
+ *     cvs_interlace_fields_f16_dev (even, odd); cvs_deinterlace_adaptive_f16_dev (prev, cur) (prev, next) (cur, next);
+ *     cvs_scale_bilinear_f32_batch_dev (sources, sources); cvs_scale_bilinear_f16_batch_dev (sources, sources);
+ *     cvs_blur_lanczos_f16_batch_dev (sources, sources); cvs_blur_over_f16_dev (source, overlays) (overlays, overlays);
+ *     cvs_blur_over_f16_batch_dev (sources, sources) (sources, overlays) (overlays, overlays)
+ * Every other device entry takes one frame, or frames against operands of another type. */
 CVS_EXPORT int cvs_frame_f16_to_f32_dev(rgba_frame_f32 *out, const rgba_frame_f16 *in, cvs_stream_t s);   /* main.c:115-139 */
 CVS_EXPORT int cvs_frame_f32_to_f16_dev(rgba_frame_f16 *out, const rgba_frame_f32 *in, cvs_stream_t s);   /* main.c:43-71 */
 CVS_EXPORT int cvs_copy_frame_f16_dev(rgba_frame_f16 *out, const rgba_frame_f16 *in, cvs_stream_t s);

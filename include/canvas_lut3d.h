@@ -45,6 +45,7 @@ typedef struct cvs_lut3d {
 CVS_EXPORT size_t cvs_lut3d_bytes(int size);                                        /* 16*N^3; 0 + message when refused */
 /* host only: N^3 * 3 floats, red fastest -> N^3 * 4 floats (the fourth 0); -1 + message for a size outside 2..65 or a value that is not finite */
 CVS_EXPORT int cvs_lut3d_pack(float *nodes4_host, const float *rgb_host, int size);
+/* target may be source's buffer, in place: canvas_hip.h "Operands that share a buffer" */
 CVS_EXPORT int cvs_lut3d_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const float *lattice_dev, const cvs_lut3d *p, cvs_stream_t s);
 CVS_EXPORT int cvs_lut3d_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const float *lattice_dev, const cvs_lut3d *p, cvs_stream_t s);
 

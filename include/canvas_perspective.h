@@ -40,6 +40,7 @@ typedef struct cvs_perspective {
     int   filter;            /* CVS_TRANSFORM_NEAREST / CVS_TRANSFORM_BILINEAR */
     int   flags;             /* none defined: 0 */
 } cvs_perspective;
+/* a target that is the source's buffer is refused: canvas_hip.h "Operands that share a buffer" */
 CVS_EXPORT int cvs_perspective_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_perspective *p, cvs_stream_t s);
 CVS_EXPORT int cvs_perspective_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_perspective *p, cvs_stream_t s);
 /* Host arithmetic, in double, every operation rounded on its own; no device needed.

@@ -53,6 +53,7 @@ typedef struct cvs_scope {
 } cvs_scope;
 CVS_EXPORT size_t cvs_scope_count(const cvs_scope *p);                       /* counters in the table; 0 + message when p is refused */
 CVS_EXPORT int cvs_scope_picture_size(const cvs_scope *p, v2i *size);        /* host only */
+/* one frame per entry, against a table of counts: nothing here falls under canvas_hip.h "Operands that share a buffer" */
 CVS_EXPORT int cvs_scope_counts_f16_dev(uint32_t *counts_dev, const rgba_frame_f16 *frame, const cvs_scope *p, cvs_stream_t s);
 CVS_EXPORT int cvs_scope_render_f16_dev(rgba_frame_f16 *target, const box2i *place, const uint32_t *counts_dev, const cvs_scope *p, float gain, cvs_stream_t s);
 /* host frame in, host table out, staged like video_frame_to_bytes */
