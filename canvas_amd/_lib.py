@@ -1,6 +1,6 @@
 """ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
-and the adaptive deinterlacer, include/canvas_scope.h, include/canvas_lut3d.h, include/canvas_perspective.h and
-include/canvas_deinterlace.h).
+the adaptive deinterlacer and the median, include/canvas_scope.h, include/canvas_lut3d.h, include/canvas_perspective.h,
+include/canvas_deinterlace.h and include/canvas_median.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -111,6 +111,18 @@ class deinterlace_params(C.Structure):
 def deinterlace_adaptive(field=0, threshold=0.02, softness=0.04, flags=0):
     """A cvs_deinterlace_adaptive for cvs_deinterlace_adaptive_f16_dev."""
     return deinterlace_params(int(field), float(threshold), float(softness), int(flags))
+
+
+MEDIAN_R, MEDIAN_G, MEDIAN_B, MEDIAN_A, MEDIAN_COLOUR, MEDIAN_ALL = 1, 2, 4, 8, 7, 15
+
+
+class median_params(C.Structure):
+    _fields_ = [("radius", C.c_int), ("threshold", C.c_float), ("channels", C.c_int), ("flags", C.c_int)]
+
+
+def median(radius=1, threshold=0.0, channels=MEDIAN_ALL, flags=0):
+    """A cvs_median for cvs_median_f16_dev / _f32_dev."""
+    return median_params(int(radius), float(threshold), int(channels), int(flags))
 
 
 class coded_image(C.Structure):
@@ -316,6 +328,12 @@ DEINTERLACE_SIGNATURES = {
     "cvs_deinterlace_adaptive_f16_dev": (C.c_int, [_F16, _F16, _F16, _F16, P(deinterlace_params), _vp]),
 }
 
+# the same for include/canvas_median.h (3 x 3 / 5 x 5 median)
+MEDIAN_SIGNATURES = {
+    "cvs_median_f16_dev": (C.c_int, [_F16, _F16, P(median_params), _vp]),
+    "cvs_median_f32_dev": (C.c_int, [_F32, _F32, P(median_params), _vp]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -342,7 +360,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -415,6 +415,19 @@ typedef struct {
 } cvk_deinterlace_params;
 int cvk_deinterlace_adaptive(const cvk_deinterlace_params *dp, int neighbours, int cus, void *stream);
 
+/* Median (median_ops.hip, DESIGN.md "Median"), f16 or f32 frames.  `w` (the window written) inside `out` and inside `cw`, the
+ * source's current window, itself inside `in`; `in` is not `out`'s buffer.  radius 1 or 2; channels a CVS_MEDIAN_* mask, not 0;
+ * gated = threshold > 0 (threshold is read only where gated, and is finite).  The launcher sets xs and seg.  One arithmetic
+ * flavour: a selection rounds nothing (the unit is not rebuilt with -DCVS_CONTRACT). */
+typedef struct {
+    cvk_view out, in;
+    cvk_rect w, cw;
+    int radius, channels, gated;
+    float threshold;
+    int xs, seg;               /* column of the first workgroup's first column-making lane; rows per segment */
+} cvk_median_params;
+int cvk_median(const cvk_median_params *mp, int half, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

@@ -136,6 +136,7 @@ int init_deint(PyObject *module);
 int init_blur(PyObject *module);
 int init_key(PyObject *module);
 int init_matte(PyObject *module);
+int init_median(PyObject *module);
 int init_transform(PyObject *module);
 int init_scope(PyObject *module);
 int init_lut3d(PyObject *module);
