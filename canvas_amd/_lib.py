@@ -1,6 +1,6 @@
 """ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
-the adaptive deinterlacer and the median, include/canvas_scope.h, include/canvas_lut3d.h, include/canvas_perspective.h,
-include/canvas_deinterlace.h and include/canvas_median.h).
+the adaptive deinterlacer, the median and the temporal denoise, include/canvas_scope.h, include/canvas_lut3d.h,
+include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h and include/canvas_temporal.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -123,6 +123,15 @@ class median_params(C.Structure):
 def median(radius=1, threshold=0.0, channels=MEDIAN_ALL, flags=0):
     """A cvs_median for cvs_median_f16_dev / _f32_dev."""
     return median_params(int(radius), float(threshold), int(channels), int(flags))
+
+
+class temporal_params(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("softness", C.c_float), ("channels", C.c_int), ("flags", C.c_int)]
+
+
+def temporal_denoise(threshold=0.02, softness=0.04, channels=MEDIAN_ALL, flags=0):
+    """A cvs_temporal_denoise for cvs_temporal_denoise_f16_dev; channels: a MEDIAN_* mask."""
+    return temporal_params(float(threshold), float(softness), int(channels), int(flags))
 
 
 class coded_image(C.Structure):
@@ -334,6 +343,11 @@ MEDIAN_SIGNATURES = {
     "cvs_median_f32_dev": (C.c_int, [_F32, _F32, P(median_params), _vp]),
 }
 
+# the same for include/canvas_temporal.h (motion-adaptive temporal denoise): out, prev2, prev1, cur, next1, next2
+TEMPORAL_SIGNATURES = {
+    "cvs_temporal_denoise_f16_dev": (C.c_int, [_F16, _F16, _F16, _F16, _F16, _F16, P(temporal_params), _vp]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -360,7 +374,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

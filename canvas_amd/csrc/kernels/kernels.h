@@ -428,6 +428,24 @@ typedef struct {
 } cvk_median_params;
 int cvk_median(const cvk_median_params *mp, int half, int cus, void *stream);
 
+/* Temporal denoise (temporal_ops.hip, DESIGN.md "Temporal denoise"), f16 frames.  `w` (the window written) inside `out` and
+ * inside `cw`, cur's current window, itself inside `cur`.  n[j], j < neighbours (1 .. 4): the neighbour frames that reach the
+ * kernel, in the contract's order of summation (prev1, next1, prev2, next2 with those left out closed up); v[j] = cw ∩ the
+ * neighbour's current window (not empty, inside n[j]): where a sample of that neighbour counts and where its weight can be more
+ * than 0.  near[j]: the index in n of the nearer frame on a far frame's side, whose weight caps n[j]'s (0 or 1, below j), or -1
+ * for a near frame.  No view is `out`'s buffer.  channels: a CVS_MEDIAN_* mask, not 0.  What host/temporal.c worked out of a
+ * cvs_temporal_denoise: soft = softness > 0, inv_soft = 1 / softness (read only where soft).  The launcher sets xs and seg.  One
+ * arithmetic flavour: every operation is rounded on its own in both (the unit is not rebuilt with -DCVS_CONTRACT). */
+typedef struct {
+    cvk_view out, cur, n[4];
+    cvk_rect w, cw, v[4];
+    int near[4];
+    int channels, soft;
+    float threshold, inv_soft;
+    int xs, seg;               /* column of lane 1 of the first workgroup (w.x0 or the pair boundary left of it); rows per segment */
+} cvk_temporal_params;
+int cvk_temporal_denoise(const cvk_temporal_params *tp, int neighbours, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

@@ -126,6 +126,11 @@ int py_scope_display(const char *name);
 bool py_scope_columns_ok(int kind, int columns);
 void py_scope_fill(cvs_scope *p, int kind, int columns, int widget, int skip, const box2i *region);
 
+/* a channel set as the nodes take it (pymedian.c): a string of distinct letters from "rgba", at least one, <-> a CVS_MEDIAN_*
+ * mask; the letters read back in the order r, g, b, a.  -1 with a TypeError or ValueError set */
+int py_channels_parse(PyObject *obj);
+PyObject *py_channels_string(int mask);
+
 int init_frames(PyObject *module);
 int init_framefuncs(PyObject *module);
 int init_animation(PyObject *module);
@@ -137,6 +142,7 @@ int init_blur(PyObject *module);
 int init_key(PyObject *module);
 int init_matte(PyObject *module);
 int init_median(PyObject *module);
+int init_temporal(PyObject *module);
 int init_transform(PyObject *module);
 int init_scope(PyObject *module);
 int init_lut3d(PyObject *module);

@@ -15,8 +15,8 @@
 
 typedef struct { node1 n; FrameFunctionHolder threshold; int radius, channels; } py_median;
 
-/* "rgba" letters, each at most once, at least one -> CVS_MEDIAN_* mask; -1 with a Python error set */
-static int parse_channels(PyObject *obj) {
+/* "rgba" letters, each at most once, at least one -> CVS_MEDIAN_* mask; -1 with a Python error set (pyext.h: pytemporal.c's too) */
+int py_channels_parse(PyObject *obj) {
     if (!obj || !PyUnicode_Check(obj)) { PyErr_SetString(PyExc_TypeError, "channels is a string of letters from \"rgba\""); return -1; }
     Py_ssize_t n;
     const char *s = PyUnicode_AsUTF8AndSize(obj, &n);
@@ -49,7 +49,7 @@ static int median_init(py_median *self, PyObject *args, PyObject *kw) {
     self->channels = CVS_MEDIAN_ALL;
     if (!PyArg_ParseTupleAndKeywords(args, kw, "O|OOO", kwlist, &src, &radius, &threshold, &channels)) return -1;
     if (radius && !(self->radius = parse_radius(radius))) return -1;
-    if (channels && (self->channels = parse_channels(channels)) < 0) return -1;
+    if (channels && (self->channels = py_channels_parse(channels)) < 0) return -1;
     if (!py_video_take_source(src, &self->n.source)) return -1;
     if (threshold && (threshold == Py_None || !py_framefunc_take_source(threshold, &self->threshold))) { if (!PyErr_Occurred()) PyErr_SetString(PyExc_TypeError, "threshold takes a number or a frame function"); return -1; }
     return 0;
@@ -106,14 +106,15 @@ static int median_set_radius(py_median *self, PyObject *v, void *closure) {
     pthread_rwlock_unlock(&self->n.lock);
     return 0;
 }
-static PyObject *median_get_channels(py_median *self, void *closure) {
+PyObject *py_channels_string(int mask) {
     char s[5];
     int n = 0;
-    for (int k = 0; k < 4; k++) if (self->channels & (1 << k)) s[n++] = "rgba"[k];
+    for (int k = 0; k < 4; k++) if (mask & (1 << k)) s[n++] = "rgba"[k];
     return PyUnicode_FromStringAndSize(s, n);
 }
+static PyObject *median_get_channels(py_median *self, void *closure) { return py_channels_string(self->channels); }
 static int median_set_channels(py_median *self, PyObject *v, void *closure) {
-    const int mask = parse_channels(v);
+    const int mask = py_channels_parse(v);
     if (mask < 0) return -1;
     py_wrlock_nogil(&self->n.lock);
     self->channels = mask;
