@@ -1,6 +1,7 @@
 """ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
 the adaptive deinterlacer, the median and the temporal denoise, include/canvas_scope.h, include/canvas_lut3d.h,
-include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h and include/canvas_temporal.h).
+include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h, include/canvas_temporal.h and
+include/canvas_ycc422.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -348,6 +349,14 @@ TEMPORAL_SIGNATURES = {
     "cvs_temporal_denoise_f16_dev": (C.c_int, [_F16, _F16, _F16, _F16, _F16, _F16, P(temporal_params), _vp]),
 }
 
+# the same for include/canvas_ycc422.h (4:2:2 Y'CbCr edges): width, height, layout, flags (0 or YCC_REC709)
+YCC422_PLANAR8, YCC422_PLANAR10, YCC422_UYVY, YCC422_V210 = 0, 1, 2, 3
+YCC422_SIGNATURES = {
+    "cvs_ycc422_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int)]),
+    "cvs_reconstruct_422_dev": (C.c_int, [_F16, P(coded_image), C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "cvs_subsample_422_dev": (C.c_int, [P(coded_image), _F16, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -374,7 +383,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -194,6 +194,8 @@ static inline cvk_dv_planes cvs_planes_view(const coded_image *p) {
     cvk_dv_planes v = { p->data[0], p->data[1], p->data[2], p->stride[0], p->stride[1], p->stride[2] };
     return v;
 }
+/* mpeg2.c: Y'CbCr -> R'G'B' row by row, Rec.601 and Rec.709 (the 4:2:0 and the 4:2:2 import edges) */
+extern const float cvs_ycc_601[9], cvs_ycc_709[9];
 
 /* ---- display.c: the display edge's cached 64 KiB byte table of (pre_lut, ramp), for the scopes.  rendering_intent 0: the
  * gamma-0.45 ramp, > 0: the widget's.  _lock returns the table with the cache's lock HELD (an eviction cannot rewrite it), or

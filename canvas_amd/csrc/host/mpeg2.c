@@ -69,9 +69,9 @@ CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame) {
 
 /* ---- the import edge: planar Y'CbCr 4:2:0 -> half RGBA ---- */
 
-/* Y'CbCr -> R'G'B', row by row, as video_reconstruct.c:55-59 (Rec.601, Poynton p. 305) and :62-66 (Rec.709, p. 316) state them */
-static const float ycc_601[9] = { 1.0f, 0.0f, 1.402f, 1.0f, -0.344136f, -0.714136f, 1.0f, 1.772f, 0.0f };
-static const float ycc_709[9] = { 1.0f, 0.0f, 1.5748f, 1.0f, -0.187324f, -0.468124f, 1.0f, 1.8556f, 0.0f };
+/* Y'CbCr -> R'G'B', row by row (shared with ycc422.c through internal.h), as video_reconstruct.c:55-59 (Rec.601, Poynton p. 305) and :62-66 (Rec.709, p. 316) state them */
+const float cvs_ycc_601[9] = { 1.0f, 0.0f, 1.402f, 1.0f, -0.344136f, -0.714136f, 1.0f, 1.772f, 0.0f };
+const float cvs_ycc_709[9] = { 1.0f, 0.0f, 1.5748f, 1.0f, -0.187324f, -0.468124f, 1.0f, 1.8556f, 0.0f };
 
 static bool recon_size_ok(int width, int height, bool progressive) {
     return width >= 2 && !(width & 1) && height >= 2 && !(height & 1) && (progressive || (height >= 4 && !(height & 3)));
@@ -105,7 +105,7 @@ CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_imag
     if (!lut) return -1;
     cvk_dv_planes pl = cvs_planes_view(planar);
     const int rc = cvk_mpeg2_reconstruct(cvs_view(frame->data, &frame->full_window), cvs_rect(&w), &pl, width, height, progressive,
-                                         (flags & CVS_YCC_REC709) ? ycc_709 : ycc_601, lut, cvs_cus(), cvs_pick_stream(stream));
+                                         (flags & CVS_YCC_REC709) ? cvs_ycc_709 : cvs_ycc_601, lut, cvs_cus(), cvs_pick_stream(stream));
     if (rc != 0) { cvs_set_error("MPEG-2 reconstruct: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     frame->current_window = w;
     return 0;

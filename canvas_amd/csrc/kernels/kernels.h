@@ -322,6 +322,19 @@ int cvk_mpeg2_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int
 int cvk_mpeg2_reconstruct(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, int width, int height, int progressive, const float mat[9],
                           const uint16_t *lut, int cus, void *stream);
 
+/* 4:2:2 Y'CbCr edges (ycc422_recon_ops.hip, ycc422_ops.hip, DESIGN.md "4:2:2 Y'CbCr edges", include/canvas_ycc422.h).  `layout`: a
+ * CVS_422_* value (the numbers below are the header's); p[1], p[2] are read for the planar layouts only.  The host has checked
+ * pointers, strides, line counts and alignment (PLANAR10: 2, V210: 4).  width even >= 2, height >= 1.  Import: the pixels of `frame`
+ * inside `w` (full window clipped to the raster; may be empty) are written, nothing else; `mat`: Y'CbCr -> R'G'B' row by row.
+ * Export: every sample of the raster is written, `w` = the current window clipped to the raster (may be empty: black); `mat`:
+ * R'G'B' -> Y'CbCr row by row.  One arithmetic flavour each (no FMA in either); `lut` = the separate flavour's table. */
+enum { CVK_422_PLANAR8 = 0, CVK_422_PLANAR10 = 1, CVK_422_UYVY = 2, CVK_422_V210 = 3 };
+typedef struct { uint8_t *p[3]; int stride[3]; } cvk_ycc422_image;
+int cvk_ycc422_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc422_image *img, int width, int height, int layout, const float mat[9],
+                           const uint16_t *lut, int cus, void *stream);
+int cvk_ycc422_subsample(const cvk_ycc422_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const float mat[9],
+                         const uint16_t *lut, int cus, void *stream);
+
 /* Field conversions on f16 frames (field_ops.hip, DESIGN.md "Field conversions").  `w`: the rectangle written, inside `out` and
  * -- field_to_frame, soften -- inside in_cur, the input's current window, itself inside `in`; interlace: inside `out` only, a
  * pixel outside the providing input's current window is zero.  One arithmetic flavour: every product is by a power of two, so

@@ -13,8 +13,8 @@
  * takes), so these nodes are where bytes cross PCIe: a reconstruction node uploads three planes
  * (DV: 518 400 bytes) and renders straight into the device frame it was given; a subsample node pulls its
  * source into a device frame, converts there and downloads the three planes.  On the device the planes of
- * either kind live in one pooled block (planes_block below); the two reconstruction nodes share one render,
- * the two subsample nodes one get_frame.
+ * either kind live in one pooled block (planes_block below); the reconstruction nodes share one render, the
+ * subsample nodes one get_frame (py_planes_render, py_planes_from_source: pyycc422.c's nodes go through them too).
  */
 #include "pyext.h"
 
@@ -150,26 +150,30 @@ static char *planes_block(coded_image *dev, const coded_image *host, cvs_stream_
 static int planes_copy(const coded_image *dev, const coded_image *host, bool up, cvs_stream_t s) {
     int rc = 0;
     for (int p = 0; rc == 0 && p < 3; p++)
-        rc = up ? cvs_memcpy_h2d(dev->data[p], host->data[p], plane_bytes(host, p), s) : cvs_memcpy_d2h(host->data[p], dev->data[p], plane_bytes(host, p), s);
+        if (plane_bytes(host, p))          /* (a one-plane layout has two planes of no bytes) */
+            rc = up ? cvs_memcpy_h2d(dev->data[p], host->data[p], plane_bytes(host, p), s) : cvs_memcpy_d2h(host->data[p], dev->data[p], plane_bytes(host, p), s);
     return rc;
 }
 
-/* The render of both reconstruction nodes (native: f16): three planes up, the device entry straight into the device slot.
- * `mpeg2`: the node's raster and flags, NULL for DV.  Planes missing or too small for the raster give an empty window (the
- * entry refuses them before any read). */
+/* The render of every reconstruction node (native: f16): the planes up, the node's device entry straight into the device slot.
+ * `planes`: how many planes the node's layout takes (the first `planes` must be there); `entry(out, dev, node, stream)`: the
+ * node's call.  Planes missing give an empty window here, planes too small for the raster at the entry (it refuses them before
+ * any read). */
 typedef struct { PyObject_HEAD CodedImageSourceHolder source; int width, height, flags; } py_mpeg2recon;
 
-static void planes_render(CodedImageSourceHolder *source, const py_mpeg2recon *mpeg2, int frame_index, rgba_frame_dev *f) {
+void py_planes_render(CodedImageSourceHolder *source, int planes, py_planes_recon entry, const void *node, int frame_index, rgba_frame_dev *f) {
     box2i_set_empty(&f->current_window);
     if (!source->source.obj || !source->source.funcs || !source->source.funcs->getFrame) return;
     coded_image *image = source->source.funcs->getFrame(source->source.obj, frame_index, 0);
     if (!image) return;
     coded_image dev;
-    char *block = image->data[0] && image->data[1] && image->data[2] ? planes_block(&dev, image, f->stream) : NULL;
+    bool have = true;
+    for (int p = 0; p < planes; p++) have = have && image->data[p];
+    char *block = have ? planes_block(&dev, image, f->stream) : NULL;
     if (block) {
         rgba_frame_f16 out = { f->data, f->full_window, f->full_window };
         int rc = planes_copy(&dev, image, true, f->stream);
-        if (rc == 0) rc = mpeg2 ? cvs_reconstruct_mpeg2_dev(&out, &dev, mpeg2->width, mpeg2->height, mpeg2->flags, f->stream) : cvs_reconstruct_dv_dev(&out, &dev, f->stream);
+        if (rc == 0) rc = entry(&out, &dev, node, f->stream);
         if (rc == 0) f->current_window = out.current_window;
         /* the host planes may be freed below: the uploads must have left them */
         cvs_stream_sync(f->stream);
@@ -178,29 +182,47 @@ static void planes_render(CodedImageSourceHolder *source, const py_mpeg2recon *m
     if (image->free_func) image->free_func(image);
 }
 
-/* The get_frame of both subsample nodes: pull the raster's window into a device frame, subsample there, download the planes.
- * DV: 720x480 at y = -1 (DVSubsampleFilter.c:55-56), chroma w/4 x h; MPEG-2: (0,0)-(w-1,h-1), chroma w/2 x h/2. */
-static coded_image *planes_from_source(video_source *source, int frame, int w, int h, bool dv) {
-    const int cw = dv ? w / 4 : w / 2, ch = dv ? h : h / 2, y0 = dv ? -1 : 0;
-    const int strides[3] = { w, cw, cw }, lines[3] = { h, ch, ch };
-    box2i window;
-    box2i_set(&window, 0, y0, w - 1, y0 + h - 1);
-    coded_image *out = coded_image_alloc(strides, lines, 3), dev;
+static int dv_recon_entry(rgba_frame_f16 *out, const coded_image *dev, const void *node, cvs_stream_t s) { return cvs_reconstruct_dv_dev(out, dev, s); }
+static int mpeg2_recon_entry(rgba_frame_f16 *out, const coded_image *dev, const void *node, cvs_stream_t s) {
+    const py_mpeg2recon *m = node;
+    return cvs_reconstruct_mpeg2_dev(out, dev, m->width, m->height, m->flags, s);
+}
+
+/* The get_frame of every subsample node: pull `window` into a device frame, subsample there through the node's device entry
+ * `entry(dev, in, node, stream)`, download the planes (`count` of them, of these strides and line counts). */
+coded_image *py_planes_from_source(video_source *source, int frame, const box2i *window, const int strides[3], const int lines[3], int count,
+                                   py_planes_sub entry, const void *node) {
+    coded_image *out = coded_image_alloc(strides, lines, count), dev;
     if (!out) return NULL;
-    rgba_frame_dev d = { cvs_pool_malloc(frame_bytes(&window, CVS_FORMAT_F16), NULL), CVS_FORMAT_F16, window, window, NULL };
+    rgba_frame_dev d = { cvs_pool_malloc(frame_bytes(window, CVS_FORMAT_F16), NULL), CVS_FORMAT_F16, *window, *window, NULL };
     char *block = planes_block(&dev, out, NULL);
     int rc = (d.data && block) ? 0 : -1;
     if (rc == 0) {
         video_get_frame_dev(source, frame, &d);
         rgba_frame_f16 in = { d.data, d.full_window, d.current_window };
-        /* DV: the pulled frame is scratch, no need to leave it encoded */
-        rc = dv ? cvs_subsample_dv_dev(&dev, &in, 0, NULL) : cvs_subsample_mpeg2_dev(&dev, &in, w, h, NULL);
+        rc = entry(&dev, &in, node, NULL);
         if (rc == 0) rc = planes_copy(&dev, out, false, NULL);
     }
     cvs_pool_free(block, NULL);
     cvs_pool_free(d.data, NULL);
     if (rc != 0) { out->free_func(out); return NULL; }
     return out;
+}
+
+/* DV: the pulled frame is scratch, no need to leave it encoded */
+static int dv_sub_entry(coded_image *dev, const rgba_frame_f16 *in, const void *node, cvs_stream_t s) { return cvs_subsample_dv_dev(dev, (rgba_frame_f16 *)in, 0, s); }
+static int mpeg2_sub_entry(coded_image *dev, const rgba_frame_f16 *in, const void *node, cvs_stream_t s) {
+    const int *size = node;
+    return cvs_subsample_mpeg2_dev(dev, in, size[0], size[1], s);
+}
+
+/* DV: 720x480 at y = -1 (DVSubsampleFilter.c:55-56), chroma w/4 x h; MPEG-2: (0,0)-(w-1,h-1), chroma w/2 x h/2. */
+static coded_image *planes_from_source(video_source *source, int frame, int w, int h, bool dv) {
+    const int cw = dv ? w / 4 : w / 2, ch = dv ? h : h / 2, y0 = dv ? -1 : 0;
+    const int strides[3] = { w, cw, cw }, lines[3] = { h, ch, ch }, size[2] = { w, h };
+    box2i window;
+    box2i_set(&window, 0, y0, w - 1, y0 + h - 1);
+    return py_planes_from_source(source, frame, &window, strides, lines, 3, dv ? dv_sub_entry : mpeg2_sub_entry, size);
 }
 
 /* ---------------------------------------------------------------- DVReconstructionFilter */
@@ -218,7 +240,7 @@ static void recon_dealloc(py_dvrecon *self) {
     Py_TYPE(self)->tp_free((PyObject *)self);
 }
 
-static void recon_render(PyObject *o, int frame_index, rgba_frame_dev *f) { planes_render(&((py_dvrecon *)o)->source, NULL, frame_index, f); }
+static void recon_render(PyObject *o, int frame_index, rgba_frame_dev *f) { py_planes_render(&((py_dvrecon *)o)->source, 3, dv_recon_entry, NULL, frame_index, f); }
 DEFINE_NODE_VTABLE(recon, CVS_FORMAT_F16, 1, 0)
 static void *recon_unused[] __attribute__((unused)) = { (void *)recon_slot_32 };
 static PyGetSetDef recon_getset[] = { { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &recon_capsule }, { NULL } };
@@ -296,7 +318,7 @@ static PyTypeObject py_type_MPEG2SubsampleFilter = {
 /* ---------------------------------------------------------------- MPEG2ReconstructionFilter */
 
 /* coded planes -> half RGBA on the device entry (DESIGN.md "MPEG-2 4:2:0 reconstruction"): the raster, the siting and the matrix
- * as keywords.  Renders like DVReconstructionFilter (planes_render above, where py_mpeg2recon is declared). */
+ * as keywords.  Renders like DVReconstructionFilter (py_planes_render above, where py_mpeg2recon is declared). */
 
 static int mpeg2r_init(py_mpeg2recon *self, PyObject *args, PyObject *kw) {
     static char *kwlist[] = { "source", "size", "interlaced", "matrix", NULL };
@@ -331,7 +353,7 @@ static void mpeg2r_dealloc(py_mpeg2recon *self) {
     Py_TYPE(self)->tp_free((PyObject *)self);
 }
 
-static void mpeg2r_render(PyObject *o, int frame_index, rgba_frame_dev *f) { planes_render(&((py_mpeg2recon *)o)->source, (py_mpeg2recon *)o, frame_index, f); }
+static void mpeg2r_render(PyObject *o, int frame_index, rgba_frame_dev *f) { py_planes_render(&((py_mpeg2recon *)o)->source, 3, mpeg2_recon_entry, o, frame_index, f); }
 DEFINE_NODE_VTABLE(mpeg2r, CVS_FORMAT_F16, 1, 0)
 static void *mpeg2r_unused[] __attribute__((unused)) = { (void *)mpeg2r_slot_32 };
 static PyGetSetDef mpeg2r_getset[] = { { VIDEO_FRAME_SOURCE_FUNCS, pyext_capsule_getter, NULL, "Video frame source C API.", &mpeg2r_capsule }, { NULL } };

@@ -131,6 +131,13 @@ void py_scope_fill(cvs_scope *p, int kind, int columns, int widget, int skip, co
 int py_channels_parse(PyObject *obj);
 PyObject *py_channels_string(int mask);
 
+/* coded planes staged on the device (pydv.c), shared by every reconstruction and subsample node: see there */
+typedef int (*py_planes_recon)(rgba_frame_f16 *out, const coded_image *dev, const void *node, cvs_stream_t s);
+typedef int (*py_planes_sub)(coded_image *dev, const rgba_frame_f16 *in, const void *node, cvs_stream_t s);
+void py_planes_render(CodedImageSourceHolder *source, int planes, py_planes_recon entry, const void *node, int frame_index, rgba_frame_dev *f);
+coded_image *py_planes_from_source(video_source *source, int frame, const box2i *window, const int strides[3], const int lines[3], int count,
+                                   py_planes_sub entry, const void *node);
+
 int init_frames(PyObject *module);
 int init_framefuncs(PyObject *module);
 int init_animation(PyObject *module);
@@ -148,6 +155,7 @@ int init_scope(PyObject *module);
 int init_lut3d(PyObject *module);
 int init_perspective(PyObject *module);
 int init_workspace(PyObject *module);
+int init_ycc422(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */
 #define DEFINE_NODE_VTABLE(P, NATIVE, HOST16, HOST32)                                                          \
