@@ -1,7 +1,7 @@
 """ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
 the adaptive deinterlacer, the median and the temporal denoise, include/canvas_scope.h, include/canvas_lut3d.h,
-include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h, include/canvas_temporal.h and
-include/canvas_ycc422.h).
+include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h, include/canvas_temporal.h,
+include/canvas_ycc422.h and include/canvas_primary.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -28,6 +28,7 @@ MAX_COORD, RESAMPLE_MAX_COORD = 1 << 30, 1 << 23        # the coordinate contrac
 SCOPE_HISTOGRAM, SCOPE_WAVEFORM, SCOPE_PARADE, SCOPE_VECTORSCOPE = range(4)      # cvs_scope.kind
 SCOPE_SKIP_TRANSPARENT, SCOPE_MAX_COLUMNS = 1, 4096                             # cvs_scope.flags and the limit of its columns
 LUT3D_MIN_SIZE, LUT3D_MAX_SIZE = 2, 65                                           # cvs_lut3d.size
+CURVES_MIN_SIZE, CURVES_MAX_SIZE, PRIMARY_MATRIX = 2, 4097, 1                    # cvs_curves.size, cvs_primary.flags
 PERSPECTIVE_MAX_SPAN = 1 << 23                                                   # cvs_perspective: how far a window may lie from its origin
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
@@ -92,6 +93,32 @@ class lut3d_params(C.Structure):
 def lut3d(size, domain_min=(0.0, 0.0, 0.0), domain_max=(1.0, 1.0, 1.0), flags=0):
     """A cvs_lut3d for the two cvs_lut3d entries: a lattice of size^3 nodes whose ends sit on domain_min and domain_max."""
     return lut3d_params(int(size), (C.c_float * 3)(*[float(v) for v in domain_min]), (C.c_float * 3)(*[float(v) for v in domain_max]), int(flags))
+
+
+class curves_params(C.Structure):
+    _fields_ = [("size", C.c_int), ("domain_min", C.c_float * 3), ("domain_max", C.c_float * 3)]
+
+
+class primary_params(C.Structure):
+    _fields_ = [("pre", curves_params), ("matrix", C.c_float * 12), ("post", curves_params), ("flags", C.c_int)]
+
+
+def curves(size=0, domain_min=(0.0, 0.0, 0.0), domain_max=(1.0, 1.0, 1.0)):
+    """A cvs_curves: three tables of `size` nodes whose ends sit on domain_min and domain_max; size 0: the stage is absent."""
+    return curves_params(int(size), (C.c_float * 3)(*[float(v) for v in domain_min]), (C.c_float * 3)(*[float(v) for v in domain_max]))
+
+
+def primary(pre=None, matrix=None, post=None, flags=None):
+    """A cvs_primary for the two cvs_primary entries.  pre / post: None (absent), a size, or (size, domain_min, domain_max);
+    matrix: None (absent) or 12 numbers, three rows of four.  flags: PRIMARY_MATRIX exactly when a matrix is given, unless stated."""
+    def stage(v):
+        if v is None:
+            return curves()
+        return curves(v) if isinstance(v, int) else curves(*v)
+    m = [0.0] * 12 if matrix is None else [float(v) for row in matrix for v in (row if hasattr(row, "__len__") else [row])]
+    if len(m) != 12:
+        raise ValueError("matrix takes 12 numbers, three rows of four")
+    return primary_params(stage(pre), (C.c_float * 12)(*m), stage(post), int((PRIMARY_MATRIX if matrix is not None else 0) if flags is None else flags))
 
 
 class perspective_params(C.Structure):
@@ -324,6 +351,14 @@ LUT3D_SIGNATURES = {
     "cvs_lut3d_f32_dev": (C.c_int, [_F32, _F32, _vp, P(lut3d_params), _vp]),
 }
 
+# the same for include/canvas_primary.h (primary colour correction: curves, matrix, curves)
+PRIMARY_SIGNATURES = {
+    "cvs_curves_bytes": (C.c_size_t, [C.c_int]),
+    "cvs_curves_pack": (C.c_int, [_f32p, _f32p, C.c_int]),
+    "cvs_primary_f16_dev": (C.c_int, [_F16, _F16, P(primary_params), _vp, _vp, _vp]),
+    "cvs_primary_f32_dev": (C.c_int, [_F32, _F32, P(primary_params), _vp, _vp, _vp]),
+}
+
 # the same for include/canvas_perspective.h (corner pin)
 PERSPECTIVE_SIGNATURES = {
     "cvs_perspective_f32_dev": (C.c_int, [_F32, _F32, P(perspective_params), _vp]),
@@ -383,7 +418,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()) + list(PRIMARY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

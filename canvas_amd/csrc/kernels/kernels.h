@@ -365,6 +365,20 @@ typedef struct {
 } cvk_lut3d_params;
 int cvk_lut3d(const cvk_lut3d_params *lp, cvk_view out, cvk_view in, cvk_rect w, int half, int cus, void *stream);
 
+/* Primary colour correction (primary_ops.hip, DESIGN.md "Primary colour correction"): `w` inside both views, which are of one
+ * format and may be the same buffer.  pre / post: a curve set's device form (kpre / kpost nodes per channel, planar R | G | B, on
+ * a 16-byte boundary) or NULL with a size of 0 for an absent stage; host/primary.c has checked 2 <= K <= 4097 and formed the
+ * scales.  m: the 3 x 4 matrix row by row, read where `matrix` is set.  At least one stage is present.  One arithmetic flavour, as
+ * the 3D LUT.  The present tables are staged in LDS by persistent workgroups: 12 * (kpre + kpost) bytes, at most 98 328. */
+typedef struct {
+    const float *pre, *post;
+    int kpre, kpost;
+    float pre_min[3], pre_scale[3], post_min[3], post_scale[3];
+    float m[12];
+    int matrix;
+} cvk_primary_params;
+int cvk_primary(const cvk_primary_params *pp, cvk_view out, cvk_view in, cvk_rect w, int half, int cus, void *stream);
+
 /* Matte refine (matte_ops.hip, DESIGN.md "Matte refine"): levels, choke and feather of the alpha channel in one launch, colour
  * carried through.  `w` (the window written) inside both views and inside `s`, the source's current window, itself inside `in`;
  * the views are of one format and NOT the same buffer.  What host/matte.c worked out of a cvs_matte: inv = 1 / (white - black)
