@@ -1,7 +1,7 @@
 """ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
 the adaptive deinterlacer, the median and the temporal denoise, include/canvas_scope.h, include/canvas_lut3d.h,
 include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h, include/canvas_temporal.h,
-include/canvas_ycc422.h and include/canvas_primary.h).
+include/canvas_ycc422.h, include/canvas_ycc420.h and include/canvas_primary.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -392,6 +392,15 @@ YCC422_SIGNATURES = {
     "cvs_subsample_422_dev": (C.c_int, [P(coded_image), _F16, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
 }
 
+# the same for include/canvas_ycc420.h (4:2:0 Y'CbCr edges): width, height, layout, flags (YCC_REC709 and the bits below)
+YCC420_PLANAR8, YCC420_PLANAR10, YCC420_NV12, YCC420_P010 = 0, 1, 2, 3
+YCC_REC2020, YCC_FULL_RANGE, YCC_SITING_CENTER, YCC_SITING_TOPLEFT, YCC_NO_TRANSFER = 4, 8, 16, 32, 64
+YCC420_SIGNATURES = {
+    "cvs_ycc420_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int)]),
+    "cvs_reconstruct_420_dev": (C.c_int, [_F16, P(coded_image), C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "cvs_subsample_420_dev": (C.c_int, [P(coded_image), _F16, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+}
+
 # the five function-pointer globals of half.c:87-91
 HALF_POINTER_GLOBALS = {
     "half_convert_to_float": C.CFUNCTYPE(None, _f32p, _u16p, C.c_int),
@@ -418,7 +427,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()) + list(PRIMARY_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()) + list(YCC420_SIGNATURES.items()) + list(PRIMARY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

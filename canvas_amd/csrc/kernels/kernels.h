@@ -335,6 +335,27 @@ int cvk_ycc422_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc422_image *i
 int cvk_ycc422_subsample(const cvk_ycc422_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const float mat[9],
                          const uint16_t *lut, int cus, void *stream);
 
+/* 4:2:0 Y'CbCr edges (ycc420_recon_ops.hip, ycc420_ops.hip, DESIGN.md "4:2:0 Y'CbCr edges", include/canvas_ycc420.h).  `layout`: a
+ * CVS_420_* value (the numbers below are the header's); p[2] is read for the planar layouts only.  The host has checked pointers,
+ * strides, line counts and alignment (the 10-bit layouts: 2).  width and height even, >= 2.  Range, matrix and siting are uniform
+ * across a launch and arrive as constants and weights:
+ *   import  code -> ((float)code - off) / div per kind; v = mid*ve[0] + above*ve[1] on even rows, mid*vo[0] + below*vo[1] on odd
+ *           ones; h = v(k)*he[0] + v(k-1)*he[1] on even columns, v(k)*ho[0] + v(k+1)*ho[1] on odd ones (a weight of 1 or 0 and a
+ *           pair of 0.5 give the contract's v(k) and (a + b) * 0.5 exactly: decoded chroma is finite, and scaling by a power of
+ *           two commutes with rounding); `left_column` != 0 where he[1] is in use (a wave then keeps a lane for column k - 1)
+ *   export  q = Y*y_scale + y_offset, C*c_scale + c_offset; code = rint(clamp(q, 0, 1) * top) clamped to [lo, hi]; siting 0 left,
+ *           1 centre, 2 top-left
+ * `lut` NULL: no table (CVS_YCC_NO_TRANSFER).  One arithmetic flavour each (no FMA in either). */
+enum { CVK_420_PLANAR8 = 0, CVK_420_PLANAR10 = 1, CVK_420_NV12 = 2, CVK_420_P010 = 3 };
+enum { CVK_420_LEFT = 0, CVK_420_CENTER = 1, CVK_420_TOPLEFT = 2 };
+typedef struct { uint8_t *p[3]; int stride[3]; } cvk_ycc420_image;
+typedef struct { float mat[9], y_off, y_div, c_off, c_div, ve[2], vo[2], he[2], ho[2]; int left_column; } cvk_ycc420_decode;
+typedef struct { float mat[9], y_scale, y_offset, c_scale, c_offset, top; unsigned lo, hi; int siting; } cvk_ycc420_encode;
+int cvk_ycc420_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc420_image *img, int width, int height, int layout, const cvk_ycc420_decode *dec,
+                           const uint16_t *lut, int cus, void *stream);
+int cvk_ycc420_subsample(const cvk_ycc420_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const cvk_ycc420_encode *enc,
+                         const uint16_t *lut, int cus, void *stream);
+
 /* Field conversions on f16 frames (field_ops.hip, DESIGN.md "Field conversions").  `w`: the rectangle written, inside `out` and
  * -- field_to_frame, soften -- inside in_cur, the input's current window, itself inside `in`; interlace: inside `out` only, a
  * pixel outside the providing input's current window is zero.  One arithmetic flavour: every product is by a power of two, so

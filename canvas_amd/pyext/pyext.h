@@ -157,6 +157,7 @@ int init_primary(PyObject *module);
 int init_perspective(PyObject *module);
 int init_workspace(PyObject *module);
 int init_ycc422(PyObject *module);
+int init_ycc420(PyObject *module);
 
 /* node vtable boilerplate: DEFINE_NODE_VTABLE(Prefix, CVS_FORMAT_F16 or _F32, host16?, host32?) */
 #define DEFINE_NODE_VTABLE(P, NATIVE, HOST16, HOST32)                                                          \
