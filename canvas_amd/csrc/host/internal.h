@@ -194,8 +194,29 @@ static inline cvk_dv_planes cvs_planes_view(const coded_image *p) {
     cvk_dv_planes v = { p->data[0], p->data[1], p->data[2], p->stride[0], p->stride[1], p->stride[2] };
     return v;
 }
-/* mpeg2.c: Y'CbCr -> R'G'B' row by row, Rec.601 and Rec.709 (the 4:2:0 and the 4:2:2 import edges) */
-extern const float cvs_ycc_601[9], cvs_ycc_709[9];
+
+/* ---- ycc_common.c: what the Y'CbCr edges share (mpeg2.c, ycc422.c, ycc420.c) ---- */
+/* the nine coefficients row by row, Y'CbCr -> R'G'B' (import) or R'G'B' -> Y'CbCr (export): Rec.2020 with CVS_YCC_REC2020, Rec.709
+ * with CVS_YCC_REC709, else Rec.601 (an entry refuses the flags it does not take before it asks) */
+const float *cvs_ycc_to_rgb(int flags);
+const float *cvs_rgb_to_ycc(int flags);
+/* the tail of cvs_ycc42x_layout: `planes` with s and l copied to whichever of the caller's arrays is there; -1 for planes == 0 (the
+ * layout or the size was refused, error set) */
+int cvs_ycc_layout_out(int planes, const int s[3], const int l[3], int strides[3], int line_counts[3]);
+/* everything an entry asks of the image, given the layout's planes, least strides, line counts and the alignment of bases and
+ * strides; 0 and *view filled, or -1 with the error set */
+int cvs_ycc_image_check(const char *what, const coded_image *image, int planes, const int strides[3], const int lines[3], int align, const char *layout_name,
+                        int width, int height, cvk_ycc_image *view);
+/* *w = `window` clipped to the width x height raster at the origin; true where nothing is left (or `window` itself is empty) */
+bool cvs_raster_window(const box2i *window, int width, int height, box2i *w);
+/* the same as the rectangle an export kernel reads inside: pixels outside the current window (and outside the raster) count as
+ * black; {0, 0, -1, -1} where nothing is left */
+cvk_rect cvs_raster_rect(const box2i *window, int width, int height);
+/* The half table of an edge, the separate flavour's in both flavours: the pixels must not depend on the flavour.  The contracted
+ * build of linear -> Rec.709 fuses a * pow - b and differs at code 0x789b; the two build Rec.709 -> linear alike today, the rule
+ * keeps it so.  NULL with the error set. */
+const half *cvs_ycc_export_lut(void);      /* linear -> Rec.709 */
+const half *cvs_ycc_import_lut(void);      /* Rec.709 -> linear (scene) */
 
 /* ---- display.c: the display edge's cached 64 KiB byte table of (pre_lut, ramp), for the scopes.  rendering_intent 0: the
  * gamma-0.45 ramp, > 0: the widget's.  _lock returns the table with the cache's lock HELD (an eviction cannot rewrite it), or

@@ -29,18 +29,11 @@ CVS_EXPORT int cvs_subsample_mpeg2_dev(coded_image *planar, const rgba_frame_f16
     }
     if (!cvs_box_contains(&frame->full_window, &frame->current_window)) { cvs_set_error("MPEG-2 subsample: current window outside the buffer"); return -1; }
     if (cvs_coords_refused("cvs_subsample_mpeg2_dev", "frame", &frame->full_window, &frame->current_window, CVS_MAX_COORD)) return -1;
-    /* pixels outside the current window (and outside the raster) count as black: the kernel reads inside w only */
-    box2i w;
-    box2i_set(&w, max(0, frame->current_window.min.x), max(0, frame->current_window.min.y),
-              min(width - 1, frame->current_window.max.x), min(height - 1, frame->current_window.max.y));
-    const cvk_rect none = { 0, 0, -1, -1 };
-    const cvk_rect r = box2i_is_empty(&frame->current_window) || box2i_is_empty(&w) ? none : cvs_rect(&w);
-    /* the separate flavour's table in both flavours: the contracted build of linear -> Rec.709 fuses a * pow - b and differs at
-     * code 0x789b, and this filter's bytes must not depend on the flavour */
-    const half *lut = cvs_lut_device_separate(CVS_LUT_LINEAR_TO_REC709);
+    const half *lut = cvs_ycc_export_lut();
     if (!lut) return -1;
     cvk_dv_planes pl = cvs_planes_view(planar);
-    CVS_KERNEL(cvk_mpeg2_subsample(&pl, cvs_view(frame->data, &frame->full_window), r, width, height, lut, cvs_cus(), cvs_pick_stream(stream)));
+    CVS_KERNEL(cvk_mpeg2_subsample(&pl, cvs_view(frame->data, &frame->full_window), cvs_raster_rect(&frame->current_window, width, height), width, height, lut,
+                                   cvs_cus(), cvs_pick_stream(stream)));
     return 0;
 }
 
@@ -69,10 +62,6 @@ CVS_EXPORT coded_image *video_subsample_mpeg2(rgba_frame_f16 *frame) {
 
 /* ---- the import edge: planar Y'CbCr 4:2:0 -> half RGBA ---- */
 
-/* Y'CbCr -> R'G'B', row by row (shared with ycc422.c through internal.h), as video_reconstruct.c:55-59 (Rec.601, Poynton p. 305) and :62-66 (Rec.709, p. 316) state them */
-const float cvs_ycc_601[9] = { 1.0f, 0.0f, 1.402f, 1.0f, -0.344136f, -0.714136f, 1.0f, 1.772f, 0.0f };
-const float cvs_ycc_709[9] = { 1.0f, 0.0f, 1.5748f, 1.0f, -0.187324f, -0.468124f, 1.0f, 1.8556f, 0.0f };
-
 static bool recon_size_ok(int width, int height, bool progressive) {
     return width >= 2 && !(width & 1) && height >= 2 && !(height & 1) && (progressive || (height >= 4 && !(height & 3)));
 }
@@ -96,16 +85,12 @@ CVS_EXPORT int cvs_reconstruct_mpeg2_dev(rgba_frame_f16 *frame, const coded_imag
         return -1;
     }
     box2i w;
-    box2i_set(&w, max(0, frame->full_window.min.x), max(0, frame->full_window.min.y), min(width - 1, frame->full_window.max.x),
-              min(height - 1, frame->full_window.max.y));
-    if (box2i_is_empty(&frame->full_window) || box2i_is_empty(&w)) return 0;
-    /* the separate flavour's table in both flavours: the pixels must not depend on the flavour (the two build this table alike
-     * today, the rule keeps it so) */
-    const half *lut = cvs_lut_device_separate(CVS_LUT_REC709_TO_LINEAR_SCENE);
+    if (cvs_raster_window(&frame->full_window, width, height, &w)) return 0;
+    const half *lut = cvs_ycc_import_lut();
     if (!lut) return -1;
     cvk_dv_planes pl = cvs_planes_view(planar);
-    const int rc = cvk_mpeg2_reconstruct(cvs_view(frame->data, &frame->full_window), cvs_rect(&w), &pl, width, height, progressive,
-                                         (flags & CVS_YCC_REC709) ? cvs_ycc_709 : cvs_ycc_601, lut, cvs_cus(), cvs_pick_stream(stream));
+    const int rc = cvk_mpeg2_reconstruct(cvs_view(frame->data, &frame->full_window), cvs_rect(&w), &pl, width, height, progressive, cvs_ycc_to_rgb(flags), lut,
+                                         cvs_cus(), cvs_pick_stream(stream));
     if (rc != 0) { cvs_set_error("MPEG-2 reconstruct: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     frame->current_window = w;
     return 0;

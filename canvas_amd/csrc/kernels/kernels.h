@@ -329,10 +329,10 @@ int cvk_mpeg2_reconstruct(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, i
  * Export: every sample of the raster is written, `w` = the current window clipped to the raster (may be empty: black); `mat`:
  * R'G'B' -> Y'CbCr row by row.  One arithmetic flavour each (no FMA in either); `lut` = the separate flavour's table. */
 enum { CVK_422_PLANAR8 = 0, CVK_422_PLANAR10 = 1, CVK_422_UYVY = 2, CVK_422_V210 = 3 };
-typedef struct { uint8_t *p[3]; int stride[3]; } cvk_ycc422_image;
-int cvk_ycc422_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc422_image *img, int width, int height, int layout, const float mat[9],
+typedef struct { uint8_t *p[3]; int stride[3]; } cvk_ycc_image;      /* the planes of a 4:2:2 or a 4:2:0 image, strides in bytes */
+int cvk_ycc422_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc_image *img, int width, int height, int layout, const float mat[9],
                            const uint16_t *lut, int cus, void *stream);
-int cvk_ycc422_subsample(const cvk_ycc422_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const float mat[9],
+int cvk_ycc422_subsample(const cvk_ycc_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const float mat[9],
                          const uint16_t *lut, int cus, void *stream);
 
 /* 4:2:0 Y'CbCr edges (ycc420_recon_ops.hip, ycc420_ops.hip, DESIGN.md "4:2:0 Y'CbCr edges", include/canvas_ycc420.h).  `layout`: a
@@ -348,12 +348,11 @@ int cvk_ycc422_subsample(const cvk_ycc422_image *img, cvk_view frame, cvk_rect w
  * `lut` NULL: no table (CVS_YCC_NO_TRANSFER).  One arithmetic flavour each (no FMA in either). */
 enum { CVK_420_PLANAR8 = 0, CVK_420_PLANAR10 = 1, CVK_420_NV12 = 2, CVK_420_P010 = 3 };
 enum { CVK_420_LEFT = 0, CVK_420_CENTER = 1, CVK_420_TOPLEFT = 2 };
-typedef struct { uint8_t *p[3]; int stride[3]; } cvk_ycc420_image;
 typedef struct { float mat[9], y_off, y_div, c_off, c_div, ve[2], vo[2], he[2], ho[2]; int left_column; } cvk_ycc420_decode;
 typedef struct { float mat[9], y_scale, y_offset, c_scale, c_offset, top; unsigned lo, hi; int siting; } cvk_ycc420_encode;
-int cvk_ycc420_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc420_image *img, int width, int height, int layout, const cvk_ycc420_decode *dec,
+int cvk_ycc420_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc_image *img, int width, int height, int layout, const cvk_ycc420_decode *dec,
                            const uint16_t *lut, int cus, void *stream);
-int cvk_ycc420_subsample(const cvk_ycc420_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const cvk_ycc420_encode *enc,
+int cvk_ycc420_subsample(const cvk_ycc_image *img, cvk_view frame, cvk_rect w, int width, int height, int layout, const cvk_ycc420_encode *enc,
                          const uint16_t *lut, int cus, void *stream);
 
 /* Field conversions on f16 frames (field_ops.hip, DESIGN.md "Field conversions").  `w`: the rectangle written, inside `out` and

@@ -19,47 +19,19 @@
 // Algorithmic bytes: 8 read + 1.5 written per source pixel; measured and what bounds it: DESIGN.md 4.5.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "pixel_math.hpp"
-#include "table_placement.hpp"
+#include "ycc_edge.hpp"
 
 namespace {
 
-using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds; using cvs::kTableLdsUnstaged;
+using cvs::v4; using cvs::v4a8; using cvs::Ycc; using cvs::fetch_pair;
 constexpr int kCols = 63;
-// beside the two placements of table_placement.hpp the diagnostic build has the LDS form without the staging copy (timing only:
-// its pixels are wrong), which isolates what the staging costs
-enum { kTableLdsUnstaged = 2 };
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t v4a8 __attribute__((ext_vector_type(4), aligned(8)));     // a pixel pair: 8-byte aligned only
+// Rec.601 R'G'B' -> Y'CbCr, as literals so that they fold into the instructions
+constexpr cvs::Mat9 kRec601 = { 0.299f, 0.587f, 0.114f, -0.168736f, -0.331264f, 0.5f, 0.5f, -0.418688f, -0.081312f };
 
-// pixels (x, y) and (x + 1, y) as four dwords {rg0, ba0, rg1, ba1}; zero where a pixel is outside `w` (w lies inside the view)
-__device__ __forceinline__ v4 fetch_pair(const cvk_view &f, const cvk_rect &w, int x, int y) {
-    v4 v = { 0u, 0u, 0u, 0u };
-    if (y < w.y0 || y > w.y1) return v;
-    const uint2 *row = reinterpret_cast<const uint2 *>(f.data) + (ptrdiff_t)(y - f.fy0) * (ptrdiff_t)f.pitch;
-    const int c = x - f.fx0;
-    if (x >= w.x0 && x + 1 <= w.x1) return __builtin_nontemporal_load(reinterpret_cast<const v4a8 *>(row + c));
-    if (x >= w.x0 && x <= w.x1) { const uint2 p = row[c]; v.x = p.x; v.y = p.y; }
-    if (x + 1 >= w.x0 && x + 1 <= w.x1) { const uint2 p = row[c + 1]; v.z = p.x; v.w = p.y; }
-    return v;
-}
-
-struct Ycc { float y, cb, cr; };
-
-__device__ __forceinline__ Ycc encode(uint32_t rg, uint32_t ba, const uint16_t *t) {
-    const float r = cvs::h2f(t[rg & 0xFFFFu]), g = cvs::h2f(t[rg >> 16]), b = cvs::h2f(t[ba & 0xFFFFu]);
-    Ycc o;       // -ffp-contract=off: each product and each sum rounds on its own
-    o.y = (r * 0.299f + g * 0.587f) + b * 0.114f;
-    o.cb = (r * -0.168736f + g * -0.331264f) + b * 0.5f;
-    o.cr = (r * 0.5f + g * -0.418688f) + b * -0.081312f;
-    return o;
-}
-
-// what GL stores into an 8-bit normalised texture: clamp (maxnum / minnum: NaN -> 0), scale, round half to even
-__device__ __forceinline__ uint32_t quantise(float v, float scale, float offset) {
-    const float q = v * scale + offset;
-    return (uint32_t)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(q, 0.0f), 1.0f) * 255.0f);
-}
+// byte = rint(clamp(Y*(219/255) + 16/255, 0, 1) * 255), likewise C with 224 and 128 (cvs::quantise)
+__device__ __forceinline__ uint32_t luma_byte(float y) { return cvs::quantise(y, 219.0f / 255.0f, 16.0f / 255.0f, 255.0f, 0u, 255u); }
+__device__ __forceinline__ uint32_t chroma_byte(float c) { return cvs::quantise(c, 224.0f / 255.0f, 128.0f / 255.0f, 255.0f, 0u, 255u); }
 
 __device__ __forceinline__ float chroma(float nm, float n0, float np, float fm, float f0, float fp) {
     float c = (3.0f / 16.0f) * nm;
@@ -69,11 +41,6 @@ __device__ __forceinline__ float chroma(float nm, float n0, float np, float fm, 
     c = c + (2.0f / 16.0f) * f0;
     c = c + (1.0f / 16.0f) * fp;
     return c;
-}
-
-__device__ __forceinline__ void store_luma_pair(uint8_t *p, uint32_t a, uint32_t b) {
-    if ((reinterpret_cast<uintptr_t>(p) & 1u) == 0) *reinterpret_cast<uint16_t *>(p) = (uint16_t)(a | (b << 8));
-    else { p[0] = (uint8_t)a; p[1] = (uint8_t)b; }
 }
 
 // the four pixel pairs (2cx, 2cx + 1) x rows 4k .. 4k + 3 of one lane; a block wholly inside `w` (every lane of a frame
@@ -122,8 +89,8 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_subsample(cvk_dv_planes pl, cvk
         Ycc e0[4], e1[4];          // columns x0, x0 + 1 of rows y0 .. y0 + 3
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            e0[r] = encode(px[r].x, px[r].y, t);
-            e1[r] = encode(px[r].z, px[r].w, t);
+            e0[r] = cvs::encode<TABLE>(px[r].x, px[r].y, kRec601, t);
+            e1[r] = cvs::encode<TABLE>(px[r].z, px[r].w, kRec601, t);
         }
 #pragma unroll
         for (int r = 0; r < 4; r++) px[r] = nx[r];
@@ -137,14 +104,13 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_subsample(cvk_dv_planes pl, cvk
         if (!live || lane == 0) continue;
 #pragma unroll
         for (int r = 0; r < 4; r++)
-            store_luma_pair(pl.y + (size_t)(y0 + r) * (size_t)pl.sy + (size_t)x0, quantise(e0[r].y, 219.0f / 255.0f, 16.0f / 255.0f),
-                            quantise(e1[r].y, 219.0f / 255.0f, 16.0f / 255.0f));
+            cvs::store_two<false>(pl.y + (size_t)(y0 + r) * (size_t)pl.sy + (size_t)x0, luma_byte(e0[r].y), luma_byte(e1[r].y));
         // field 0: near row 0, far row 2; field 1: near row 3, far row 1 (of the group)
         const size_t c0 = (size_t)(2 * k), c1 = c0 + 1;
-        pl.cb[c0 * (size_t)pl.scb + cx] = (uint8_t)quantise(chroma(lcb[0], e0[0].cb, e1[0].cb, lcb[2], e0[2].cb, e1[2].cb), 224.0f / 255.0f, 128.0f / 255.0f);
-        pl.cr[c0 * (size_t)pl.scr + cx] = (uint8_t)quantise(chroma(lcr[0], e0[0].cr, e1[0].cr, lcr[2], e0[2].cr, e1[2].cr), 224.0f / 255.0f, 128.0f / 255.0f);
-        pl.cb[c1 * (size_t)pl.scb + cx] = (uint8_t)quantise(chroma(lcb[3], e0[3].cb, e1[3].cb, lcb[1], e0[1].cb, e1[1].cb), 224.0f / 255.0f, 128.0f / 255.0f);
-        pl.cr[c1 * (size_t)pl.scr + cx] = (uint8_t)quantise(chroma(lcr[3], e0[3].cr, e1[3].cr, lcr[1], e0[1].cr, e1[1].cr), 224.0f / 255.0f, 128.0f / 255.0f);
+        pl.cb[c0 * (size_t)pl.scb + cx] = (uint8_t)chroma_byte(chroma(lcb[0], e0[0].cb, e1[0].cb, lcb[2], e0[2].cb, e1[2].cb));
+        pl.cr[c0 * (size_t)pl.scr + cx] = (uint8_t)chroma_byte(chroma(lcr[0], e0[0].cr, e1[0].cr, lcr[2], e0[2].cr, e1[2].cr));
+        pl.cb[c1 * (size_t)pl.scb + cx] = (uint8_t)chroma_byte(chroma(lcb[3], e0[3].cb, e1[3].cb, lcb[1], e0[1].cb, e1[1].cb));
+        pl.cr[c1 * (size_t)pl.scr + cx] = (uint8_t)chroma_byte(chroma(lcr[3], e0[3].cr, e1[3].cr, lcr[1], e0[1].cr, e1[1].cr));
     }
 }
 
@@ -159,16 +125,15 @@ static void launch(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int widt
 
 extern "C" int cvk_mpeg2_subsample(const cvk_dv_planes *pl, cvk_view frame, cvk_rect w, int width, int height, const uint16_t *lut, int cus, void *stream) {
     if (width < 2 || (width & 1) || height < 4 || (height & 3)) return (int)hipErrorInvalidValue;
-    const long long chunks = ((long long)(width / 2) + kCols - 1) / kCols, units = chunks * (long long)(height / 4);
-    if (units > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
-    const long long n = cus > 0 ? cus : 256;
+    const long long chunks = ((long long)(width / 2) + kCols - 1) / kCols, pixels = (long long)width * (long long)height;
+    cvs::StripPlan p;      // a unit is one row group: strips of 1
+    if (!cvs::plan_strips(chunks, height / 4, pixels, true, cus > 0 ? cus : 256, 1, &p)) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    const int table = cvs::table_placement((long long)width * (long long)height);
-    const long long most = cvs::table_workgroups(table, n);
-    if (table == kTableL2) launch<kTableL2, cvs::kTableL2Lanes>(pl, frame, w, width, chunks, units, lut, most, s);
 #ifdef CVS_DIAG
-    else if (table == kTableLdsUnstaged) launch<kTableLdsUnstaged, cvs::kTableLdsLanes>(pl, frame, w, width, chunks, units, lut, most, s);
+    if (cvs::table_placement(pixels) == kTableLdsUnstaged)
+        launch<kTableLdsUnstaged, cvs::kTableLdsLanes>(pl, frame, w, width, chunks, p.units, lut, p.most, s);
+    else
 #endif
-    else launch<kTableLds, cvs::kTableLdsLanes>(pl, frame, w, width, chunks, units, lut, most, s);
+    cvs::with_table(p.table, [&](auto TABLE, auto LANES) { launch<TABLE(), LANES()>(pl, frame, w, width, chunks, p.units, lut, p.most, s); });
     return (int)hipGetLastError();
 }

@@ -27,19 +27,15 @@
 // Algorithmic bytes: 1.5 read + 8 written per pixel.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "pixel_math.hpp"
-#include "table_placement.hpp"
+#include "ycc_edge.hpp"
 
 namespace {
 
-using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds; using cvs::clampi; using cvs::Mat9;
 constexpr int kCols = 63, kMaxStrip = 16;
 enum { kInterlaced = 0, kProgressive = 1 };
 // the chroma rows a group keeps: interlaced {field 0: j-1, j, j+1; field 1: j-1, j, j+1}, progressive {2j-1, 2j, 2j+1, 2j+2}
 template <int SITING> struct Ring { static constexpr int n = SITING == kInterlaced ? 6 : 4; };
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // plane row of ring slot s for group j; slots 0..2 / 3..5 are field rows j-1 .. j+1 of field 0 / 1 (interlaced)
 template <int SITING>
@@ -105,32 +101,18 @@ __device__ __forceinline__ float vertical(const float (&c)[Ring<SITING>::n], int
     }
 }
 
-struct Mat { float m0, m1, m2, m3, m4, m5, m6, m7, m8; };
-
-// one pixel: {rg, ba} codes after the table (-ffp-contract=off: every product and sum rounds on its own)
-__device__ __forceinline__ uint2 pixel(float yf, float cb, float cr, const Mat &m, const uint16_t *t, uint32_t alpha) {
-    const float r = (yf * m.m0 + cb * m.m1) + cr * m.m2;
-    const float g = (yf * m.m3 + cb * m.m4) + cr * m.m5;
-    const float b = (yf * m.m6 + cb * m.m7) + cr * m.m8;
-    const uint32_t rg = cvs::f2h_rz2(r, g), bc = cvs::f2h_rz(b);
-    return make_uint2((uint32_t)t[rg & 0xFFFFu] | ((uint32_t)t[rg >> 16] << 16), (uint32_t)t[bc] | (alpha << 16));
-}
-
 // units: (strip of `strip` row groups, run of kCols chroma columns) over the window's groups [ja, jb] and columns [ka, ...];
 // `chunks` runs per strip, so the waves of neighbouring units write neighbouring parts of the same rows.  A wave's unit is
 // wave-uniform.
 template <int SITING, int TABLE, int LANES>
-__global__ __launch_bounds__(LANES) void k_mpeg2_reconstruct(cvk_view frame, cvk_rect w, cvk_dv_planes pl, Mat m, int width, int height, int ka,
+__global__ __launch_bounds__(LANES) void k_mpeg2_reconstruct(cvk_view frame, cvk_rect w, cvk_dv_planes pl, Mat9 m, int width, int height, int ka,
                                                              int ja, int jb, int strip, int chunks, int units, const uint16_t *__restrict__ lut) {
     constexpr int kWaves = LANES / 64, NR = Ring<SITING>::n;
     __shared__ __attribute__((aligned(16))) uint16_t lds[kTable];
     __shared__ float dec_y[256], dec_c[256];
     const uint16_t *t = TABLE == kTableL2 ? lut : lds;
     if (TABLE == kTableLds) cvs::stage_table<LANES>(lds, lut);      // (the wait is the __syncthreads() below)
-    for (int i = threadIdx.x; i < 256; i += LANES) {
-        dec_y[i] = ((float)i - 16.0f) / 219.0f;
-        dec_c[i] = ((float)i - 128.0f) / 224.0f;
-    }
+    cvs::build_decode<256, LANES>(dec_y, dec_c, 16.0f, 219.0f, 128.0f, 224.0f);
     __syncthreads();
     const uint32_t alpha = t[0x3C00u];                     // f2h_rz(1.0f)
     const int lane = (int)(threadIdx.x & 63u), cw = width >> 1, stride = (int)gridDim.x * kWaves;
@@ -161,15 +143,10 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_reconstruct(cvk_view frame, cvk
                 const float vb = vertical<SITING>(cb, r), vr = vertical<SITING>(cr, r);
                 const float vb1 = __shfl_down(vb, 1), vr1 = __shfl_down(vr, 1);
                 const float hb = (vb + vb1) * 0.5f, hr = (vr + vr1) * 0.5f;
-                const uint2 p0 = pixel(dec_y[cur.y[r] & 0xFFu], vb, vr, m, t, alpha);
-                const uint2 p1 = pixel(dec_y[cur.y[r] >> 8], hb, hr, m, t, alpha);
+                const uint2 p0 = cvs::pixel<TABLE>(dec_y[cur.y[r] & 0xFFu], vb, vr, m, t, alpha);
+                const uint2 p1 = cvs::pixel<TABLE>(dec_y[cur.y[r] >> 8], hb, hr, m, t, alpha);
                 uint2 *o = reinterpret_cast<uint2 *>(frame.data) + (ptrdiff_t)(y - frame.fy0) * (ptrdiff_t)frame.pitch + (x - frame.fx0);
-                if (in0 && in1 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0)
-                    __builtin_nontemporal_store(v4{ p0.x, p0.y, p1.x, p1.y }, reinterpret_cast<v4 *>(o));
-                else {
-                    if (in0) o[0] = p0;
-                    if (in1) o[1] = p1;
-                }
+                cvs::store_pixel_pair<true>(o, p0, p1, in0, in1);
             }
             cur = nxt;
             if (j < j1) {
@@ -186,24 +163,10 @@ __global__ __launch_bounds__(LANES) void k_mpeg2_reconstruct(cvk_view frame, cvk
 }
 
 template <int SITING, int TABLE, int LANES>
-static void launch(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, const Mat &m, int width, int height, int ka, int ja, int jb, int strip,
-                   long long chunks, long long units, const uint16_t *lut, long long most, hipStream_t s) {
-    hipLaunchKernelGGL((k_mpeg2_reconstruct<SITING, TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, frame, w, *pl, m, width,
-                       height, ka, ja, jb, strip, (int)chunks, (int)units, lut);
-}
-
-// The strip is the fewest row groups that leave no unit without a wave: one trip per wave, no second round for a few waves.  Some
-// CUs may stay idle (4K interlaced: 210 of 256 workgroups); handing every wave an equal share instead fills them all but spreads
-// neighbouring waves' stores over rows far apart, and measured slower at 4K.
-template <int SITING>
-static void dispatch(int table, cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, const Mat &m, int width, int height, int ka, int ja, int jb,
-                     long long chunks, long long groups, const uint16_t *lut, long long cus, hipStream_t s) {
-    const long long lanes = table == kTableL2 ? cvs::kTableL2Lanes : cvs::kTableLdsLanes, most = cvs::table_workgroups(table, cus), waves = most * (lanes / 64);
-    long long strip = (chunks * groups + waves - 1) / waves;
-    strip = strip < 1 ? 1 : (strip > kMaxStrip ? kMaxStrip : strip);
-    const long long units = chunks * ((groups + strip - 1) / strip);
-    if (table == kTableL2) launch<SITING, kTableL2, cvs::kTableL2Lanes>(frame, w, pl, m, width, height, ka, ja, jb, (int)strip, chunks, units, lut, most, s);
-    else launch<SITING, kTableLds, cvs::kTableLdsLanes>(frame, w, pl, m, width, height, ka, ja, jb, (int)strip, chunks, units, lut, most, s);
+static void launch(cvk_view frame, cvk_rect w, const cvk_dv_planes *pl, const Mat9 &m, int width, int height, int ka, int ja, int jb, long long chunks,
+                   const cvs::StripPlan &p, const uint16_t *lut, hipStream_t s) {
+    hipLaunchKernelGGL((k_mpeg2_reconstruct<SITING, TABLE, LANES>), cvs::table_grid<LANES>(p.units, p.most), dim3(LANES), 0, s, frame, w, *pl, m, width,
+                       height, ka, ja, jb, (int)p.strip, (int)chunks, (int)p.units, lut);
 }
 
 }  // namespace
@@ -215,13 +178,13 @@ extern "C" int cvk_mpeg2_reconstruct(cvk_view frame, cvk_rect w, const cvk_dv_pl
     if (w.x0 < 0 || w.y0 < 0 || w.x1 >= width || w.y1 >= height) return (int)hipErrorInvalidValue;
     const int ka = w.x0 >> 1, ja = w.y0 >> 2, jb = w.y1 >> 2;
     const long long chunks = ((long long)(w.x1 >> 1) - ka + kCols) / kCols, groups = (long long)jb - ja + 1;
-    if (chunks * groups > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
-    const Mat m = { mat[0], mat[1], mat[2], mat[3], mat[4], mat[5], mat[6], mat[7], mat[8] };
-    const long long n = cus > 0 ? cus : 256;
+    cvs::StripPlan p;      // strips of row groups
+    if (!cvs::plan_strips(chunks, groups, (long long)width * (long long)height, true, cus > 0 ? cus : 256, kMaxStrip, &p)) return (int)hipErrorInvalidValue;
+    const Mat9 m = cvs::mat9(mat);
     hipStream_t s = (hipStream_t)stream;
-    // (the diagnostic build's CVS_MPEG2_TABLE: any value other than the L2 form's means LDS here)
-    const int table = cvs::table_placement((long long)width * (long long)height) == kTableL2 ? kTableL2 : kTableLds;
-    if (progressive) dispatch<kProgressive>(table, frame, w, pl, m, width, height, ka, ja, jb, chunks, groups, lut, n, s);
-    else dispatch<kInterlaced>(table, frame, w, pl, m, width, height, ka, ja, jb, chunks, groups, lut, n, s);
+    cvs::with_table(p.table, [&](auto TABLE, auto LANES) {
+        if (progressive) launch<kProgressive, TABLE(), LANES()>(frame, w, pl, m, width, height, ka, ja, jb, chunks, p, lut, s);
+        else launch<kInterlaced, TABLE(), LANES()>(frame, w, pl, m, width, height, ka, ja, jb, chunks, p, lut, s);
+    });
     return (int)hipGetLastError();
 }

@@ -1,6 +1,7 @@
-// table_placement.hpp -- where the 128 KiB half -> half table of a 4:2:0 kernel lives, and the persistent launch that goes with
-// it (k_mpeg2_subsample, k_mpeg2_reconstruct).  color_ops.hip / chain_kernel.hpp keep table copies of their own, shaped by
-// those kernels' pipelining.
+// table_placement.hpp -- where the 128 KiB half -> half table of a Y'CbCr edge kernel lives, and the persistent launch that goes
+// with it: k_mpeg2_subsample, k_mpeg2_reconstruct, k_ycc422_subsample, k_ycc422_reconstruct, k_ycc420_subsample and
+// k_ycc420_reconstruct (what else those six share: ycc_edge.hpp).  color_ops.hip / chain_kernel.hpp keep table copies of their own,
+// shaped by those kernels' pipelining.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
@@ -9,8 +10,10 @@ namespace cvs {
 
 constexpr int kTable = 65536;          // entries: one per half code
 // Staged into LDS by 1024-lane workgroups, one per CU (the table fills the LDS), or gathered from L2 through the vector L1 by
-// 256-lane workgroups, six per CU.
-enum { kTableLds = 0, kTableL2 = 1 };
+// 256-lane workgroups, six per CU.  Or absent (the 4:2:0 edges without a transfer curve): launched like the gathered form.
+// kTableLdsUnstaged is the diagnostic build's LDS form without the staging copy (k_mpeg2_subsample, timing only: its pixels are
+// wrong), which isolates what the staging costs.
+enum { kTableLds = 0, kTableL2 = 1, kTableNone = 2, kTableLdsUnstaged = 3 };
 constexpr int kTableLdsLanes = 1024, kTableL2Lanes = 256, kTableL2PerCu = 6;
 // Chosen by measurement (profiles/mpeg2): staging costs every workgroup ~2 us before its first pixel, which a small raster does
 // not earn back.  Kernel medians gathering vs staged, us:
@@ -35,8 +38,10 @@ __device__ __forceinline__ void stage_table(uint16_t *lds, const uint16_t *lut) 
     for (int i = threadIdx.x; i < kTable * 2 / 16; i += LANES) dst[i] = src[i];
 }
 
-// the persistent launch: at most this many workgroups on `cus` CUs ...
-inline long long table_workgroups(int table, long long cus) { return table == kTableL2 ? cus * kTableL2PerCu : cus; }
+// the persistent launch: workgroups of this many lanes, at most this many of them on `cus` CUs ...
+inline bool table_in_lds(int table) { return table == kTableLds || table == kTableLdsUnstaged; }
+inline long long table_lanes(int table) { return table_in_lds(table) ? kTableLdsLanes : kTableL2Lanes; }
+inline long long table_workgroups(int table, long long cus) { return table_in_lds(table) ? cus : cus * kTableL2PerCu; }
 // ... and no workgroup without a unit of work of its own (one unit per wave and trip)
 template <int LANES>
 inline dim3 table_grid(long long units, long long most) {

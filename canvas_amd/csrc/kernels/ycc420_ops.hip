@@ -1,7 +1,7 @@
 // ycc420_ops.hip -- the 4:2:0 export edge: half RGBA -> planar 8/10-bit, NV12 or P010 Y'CbCr, progressive (include/canvas_ycc420.h).
 //
 //   k_ycc420_subsample   no reference code; the 4:2:2 export edge (ycc422_ops.hip) with a vertical step in front of its chroma
-//                        filter, every rounding fixed (DESIGN.md "4:2:0 Y'CbCr edges"):
+//                        filter, every rounding fixed (DESIGN.md "4:2:0 Y'CbCr edges"; fetch, encode, quantise, tent: ycc_edge.hpp):
 //     P(x, y)   the frame's half RGBA inside the window `w` (current_window clipped to the raster), else 0; column -1 reads
 //               column 0 and row -1 row 0; alpha ignored.
 //     encode    r, g, b through the linear -> Rec.709 half table where there is one, widened to f32; the matrix, every product
@@ -28,13 +28,12 @@
 // Algorithmic bytes per pixel: 8 read; 1.5 (8-bit) or 3 (10-bit) written.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "pixel_math.hpp"
-#include "table_placement.hpp"
+#include "ycc_edge.hpp"
 
 namespace {
 
-using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
-enum { kTableNone = 2 };
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds; using cvs::kTableNone;
+using cvs::v4; using cvs::Mat9; using cvs::Ycc; using cvs::encode; using cvs::tent; using cvs::store_two;
 constexpr int kRun = 63, kMaxStrip = 32;
 enum { kP8 = CVK_420_PLANAR8, kP10 = CVK_420_PLANAR10, kNv12 = CVK_420_NV12, kP010 = CVK_420_P010 };
 template <int L> struct Lay {
@@ -42,73 +41,27 @@ template <int L> struct Lay {
     static constexpr bool semi = L == kNv12 || L == kP010;            // Cb and Cr interleaved in plane 1
     static constexpr int shift = L == kP010 ? 6 : 0;                  // where a code sits in its sample
 };
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t v4a8 __attribute__((ext_vector_type(4), aligned(8)));     // a pixel pair: 8-byte aligned only
 
-__device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-// pixels (x, y) and (x + 1, y) as four dwords {rg0, ba0, rg1, ba1}; zero where a pixel is outside `w` (w lies inside the view) or
-// the block is left or right of the raster (k < 0: lane 0 at the left edge)
-__device__ __forceinline__ v4 fetch_pair(const cvk_view &f, const cvk_rect &w, int k, int y) {
-    v4 v = { 0u, 0u, 0u, 0u };
-    const long long x = 2LL * k;
-    if (k < 0 || y < w.y0 || y > w.y1 || x + 1 < w.x0 || x > w.x1) return v;
-    const uint2 *p = reinterpret_cast<const uint2 *>(f.data) + (ptrdiff_t)(y - f.fy0) * (ptrdiff_t)f.pitch + (x - f.fx0);
-    if (x >= w.x0 && x + 1 <= w.x1) return __builtin_nontemporal_load(reinterpret_cast<const v4a8 *>(p));
-    if (x >= w.x0) { const uint2 a = p[0]; v.x = a.x; v.y = a.y; }
-    if (x + 1 <= w.x1) { const uint2 a = p[1]; v.z = a.x; v.w = a.y; }
-    return v;
+// the pixel pair (2k, 2k + 1) of row y (cvs::fetch_pair); zero too where the block is left of the raster (k < 0: lane 0 at the
+// left edge)
+__device__ __forceinline__ v4 block_row(const cvk_view &f, const cvk_rect &w, int k, int y) {
+    if (k < 0) return v4{ 0u, 0u, 0u, 0u };
+    return cvs::fetch_pair(f, w, 2LL * k, y);
 }
 
 struct Coef {
-    float m0, m1, m2, m3, m4, m5, m6, m7, m8;
+    Mat9 m;
     float y_scale, y_offset, c_scale, c_offset, top;
     uint32_t lo, hi;
     int siting;
 };
-struct Ycc { float y, cb, cr; };
 
-template <int TABLE>
-__device__ __forceinline__ Ycc encode(uint32_t rg, uint32_t ba, const Coef &m, const uint16_t *t) {
-    float r, g, b;
-    if constexpr (TABLE == kTableNone) { r = cvs::h2f(rg & 0xFFFFu); g = cvs::h2f(rg >> 16); b = cvs::h2f(ba & 0xFFFFu); }
-    else { r = cvs::h2f(t[rg & 0xFFFFu]); g = cvs::h2f(t[rg >> 16]); b = cvs::h2f(t[ba & 0xFFFFu]); }
-    Ycc o;       // -ffp-contract=off: each product and each sum rounds on its own
-    o.y = (r * m.m0 + g * m.m1) + b * m.m2;
-    o.cb = (r * m.m3 + g * m.m4) + b * m.m5;
-    o.cr = (r * m.m6 + g * m.m7) + b * m.m8;
-    return o;
-}
-
-// clamp (maxnum / minnum: NaN -> 0), scale, round half to even, the code's own clamp
-__device__ __forceinline__ uint32_t quantise(float v, float scale, float offset, const Coef &m) {
-    const float q = v * scale + offset;
-    const uint32_t code = (uint32_t)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(q, 0.0f), 1.0f) * m.top);
-    return min(max(code, m.lo), m.hi);
-}
-
-__device__ __forceinline__ float tent(float a, float b, float c) {
-    float v = 0.25f * a;
-    v = v + 0.5f * b;
-    v = v + 0.25f * c;
-    return v;
-}
-
-// two neighbouring samples: 8-bit one 16-bit store, 10-bit one 32-bit store, where aligned; sample by sample otherwise
-template <bool TEN>
-__device__ __forceinline__ void store_two(uint8_t *p, uint32_t a, uint32_t b) {
-    if constexpr (TEN) {
-        if (aligned(p, 4)) *reinterpret_cast<uint32_t *>(p) = a | (b << 16);
-        else { reinterpret_cast<uint16_t *>(p)[0] = (uint16_t)a; reinterpret_cast<uint16_t *>(p)[1] = (uint16_t)b; }
-    } else {
-        if (aligned(p, 2)) *reinterpret_cast<uint16_t *>(p) = (uint16_t)(a | (b << 8));
-        else { p[0] = (uint8_t)a; p[1] = (uint8_t)b; }
-    }
-}
+__device__ __forceinline__ uint32_t luma_code(float v, const Coef &m) { return cvs::quantise(v, m.y_scale, m.y_offset, m.top, m.lo, m.hi); }
+__device__ __forceinline__ uint32_t chroma_code(float v, const Coef &m) { return cvs::quantise(v, m.c_scale, m.c_offset, m.top, m.lo, m.hi); }
 
 // units: (strip of `strip` chroma rows, run of kRun blocks); `chunks` runs per strip.  A wave's unit is wave-uniform.
 template <int L, int TABLE, int LANES>
-__global__ __launch_bounds__(LANES) void k_ycc420_subsample(cvk_ycc420_image im, cvk_view frame, cvk_rect w, Coef m, int width, int height, int strip,
+__global__ __launch_bounds__(LANES) void k_ycc420_subsample(cvk_ycc_image im, cvk_view frame, cvk_rect w, Coef m, int width, int height, int strip,
                                                             int chunks, int units, const uint16_t *__restrict__ lut) {
     constexpr int kWaves = LANES / 64, B = Lay<L>::ten ? 2 : 1, SH = Lay<L>::shift;
     constexpr bool TEN = Lay<L>::ten;
@@ -119,8 +72,8 @@ __global__ __launch_bounds__(LANES) void k_ycc420_subsample(cvk_ycc420_image im,
     v4 p0 = { 0u, 0u, 0u, 0u }, p1 = { 0u, 0u, 0u, 0u };
     if (u < units) {                                       // the first unit's first pair: before the table is staged
         const int s = u / chunks, k = (u - s * chunks) * kRun + lane - 1;
-        p0 = fetch_pair(frame, w, k, 2 * s * strip);
-        p1 = fetch_pair(frame, w, k, 2 * s * strip + 1);
+        p0 = block_row(frame, w, k, 2 * s * strip);
+        p1 = block_row(frame, w, k, 2 * s * strip + 1);
     }
     if (TABLE == kTableLds) {
         cvs::stage_table<LANES>(lds, lut);
@@ -130,25 +83,25 @@ __global__ __launch_bounds__(LANES) void k_ycc420_subsample(cvk_ycc420_image im,
         const int s = u / chunks, k = (u - s * chunks) * kRun + lane - 1;
         const int c0 = s * strip, c1 = min(c0 + strip - 1, ch - 1);
         if (!fresh) {
-            p0 = fetch_pair(frame, w, k, 2 * c0);
-            p1 = fetch_pair(frame, w, k, 2 * c0 + 1);
+            p0 = block_row(frame, w, k, 2 * c0);
+            p1 = block_row(frame, w, k, 2 * c0 + 1);
         }
         // E(2c - 1) of both columns: the row above the strip, row -1 reading row 0 (top-left siting only; wave-uniform)
         float ab0 = 0.0f, ar0 = 0.0f, ab1 = 0.0f, ar1 = 0.0f;
         if (m.siting == CVK_420_TOPLEFT) {
-            const v4 pa = fetch_pair(frame, w, k, max(2 * c0 - 1, 0));
-            const Ycc a0 = encode<TABLE>(pa.x, pa.y, m, t), a1 = encode<TABLE>(pa.z, pa.w, m, t);
+            const v4 pa = block_row(frame, w, k, max(2 * c0 - 1, 0));
+            const Ycc a0 = encode<TABLE>(pa.x, pa.y, m.m, t), a1 = encode<TABLE>(pa.z, pa.w, m.m, t);
             ab0 = a0.cb; ar0 = a0.cr; ab1 = a1.cb; ar1 = a1.cr;
         }
         for (int c = c0; c <= c1; c++) {
             v4 n0 = { 0u, 0u, 0u, 0u }, n1 = { 0u, 0u, 0u, 0u };
             if (c < c1) {
-                n0 = fetch_pair(frame, w, k, 2 * c + 2);
-                n1 = fetch_pair(frame, w, k, 2 * c + 3);
+                n0 = block_row(frame, w, k, 2 * c + 2);
+                n1 = block_row(frame, w, k, 2 * c + 3);
             }
             // rows 2c (e0) and 2c + 1 (e1), columns 2k (x) and 2k + 1 (y)
-            const Ycc e0x = encode<TABLE>(p0.x, p0.y, m, t), e0y = encode<TABLE>(p0.z, p0.w, m, t);
-            const Ycc e1x = encode<TABLE>(p1.x, p1.y, m, t), e1y = encode<TABLE>(p1.z, p1.w, m, t);
+            const Ycc e0x = encode<TABLE>(p0.x, p0.y, m.m, t), e0y = encode<TABLE>(p0.z, p0.w, m.m, t);
+            const Ycc e1x = encode<TABLE>(p1.x, p1.y, m.m, t), e1y = encode<TABLE>(p1.z, p1.w, m.m, t);
             p0 = n0; p1 = n1;
             float vbx, vrx, vby, vry;      // V of columns 2k and 2k + 1
             if (m.siting == CVK_420_TOPLEFT) {
@@ -165,10 +118,10 @@ __global__ __launch_bounds__(LANES) void k_ycc420_subsample(cvk_ycc420_image im,
             if (k < 0 || k >= cw || lane == 0) continue;
             const float cbv = m.siting == CVK_420_CENTER ? (vbx + vby) * 0.5f : tent(lb, vbx, vby);
             const float crv = m.siting == CVK_420_CENTER ? (vrx + vry) * 0.5f : tent(lr, vrx, vry);
-            const uint32_t bc = quantise(cbv, m.c_scale, m.c_offset, m) << SH, rc = quantise(crv, m.c_scale, m.c_offset, m) << SH;
+            const uint32_t bc = chroma_code(cbv, m) << SH, rc = chroma_code(crv, m) << SH;
             uint8_t *py = im.p[0] + (size_t)(2 * c) * (size_t)im.stride[0] + (size_t)(2 * B) * (size_t)k;
-            store_two<TEN>(py, quantise(e0x.y, m.y_scale, m.y_offset, m) << SH, quantise(e0y.y, m.y_scale, m.y_offset, m) << SH);
-            store_two<TEN>(py + (size_t)im.stride[0], quantise(e1x.y, m.y_scale, m.y_offset, m) << SH, quantise(e1y.y, m.y_scale, m.y_offset, m) << SH);
+            store_two<TEN>(py, luma_code(e0x.y, m) << SH, luma_code(e0y.y, m) << SH);
+            store_two<TEN>(py + (size_t)im.stride[0], luma_code(e1x.y, m) << SH, luma_code(e1y.y, m) << SH);
             if constexpr (Lay<L>::semi) store_two<TEN>(im.p[1] + (size_t)c * (size_t)im.stride[1] + (size_t)(2 * B) * (size_t)k, bc, rc);
             else {
                 uint8_t *pb = im.p[1] + (size_t)c * (size_t)im.stride[1] + (size_t)B * (size_t)k;
@@ -181,41 +134,31 @@ __global__ __launch_bounds__(LANES) void k_ycc420_subsample(cvk_ycc420_image im,
 }
 
 template <int L, int TABLE, int LANES>
-static void launch(const cvk_ycc420_image *im, cvk_view frame, cvk_rect w, const Coef &m, int width, int height, int strip, long long chunks, long long units,
-                   const uint16_t *lut, long long most, hipStream_t s) {
-    hipLaunchKernelGGL((k_ycc420_subsample<L, TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, *im, frame, w, m, width, height, strip,
-                       (int)chunks, (int)units, lut);
+static void launch(const cvk_ycc_image *im, cvk_view frame, cvk_rect w, const Coef &m, int width, int height, long long chunks, const cvs::StripPlan &p,
+                   const uint16_t *lut, hipStream_t s) {
+    hipLaunchKernelGGL((k_ycc420_subsample<L, TABLE, LANES>), cvs::table_grid<LANES>(p.units, p.most), dim3(LANES), 0, s, *im, frame, w, m, width, height,
+                       (int)p.strip, (int)chunks, (int)p.units, lut);
 }
 
-// The strip is the fewest chroma rows that leave no unit without a wave (one trip per wave where the raster allows it).  Without
-// a table the launch is the gathered form's: small workgroups, several per CU.
 template <int L>
-static int dispatch(const cvk_ycc420_image *im, cvk_view frame, cvk_rect w, const Coef &m, int width, int height, const uint16_t *lut, long long cus,
+static int dispatch(const cvk_ycc_image *im, cvk_view frame, cvk_rect w, const Coef &m, int width, int height, const uint16_t *lut, long long cus,
                     hipStream_t s) {
-    const long long chunks = ((long long)(width / 2) + kRun - 1) / kRun, rows = height / 2;
-    if (chunks * rows > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
-    // (the diagnostic build's CVS_MPEG2_TABLE: any value other than the L2 form's means LDS here)
-    const int table = !lut ? kTableNone : (cvs::table_placement((long long)width * (long long)height) == kTableL2 ? kTableL2 : kTableLds);
-    const long long lanes = table == kTableLds ? cvs::kTableLdsLanes : cvs::kTableL2Lanes;
-    const long long most = cvs::table_workgroups(table == kTableLds ? kTableLds : kTableL2, cus), waves = most * (lanes / 64);
-    long long strip = (chunks * rows + waves - 1) / waves;
-    strip = strip < 1 ? 1 : (strip > kMaxStrip ? kMaxStrip : strip);
-    const long long units = chunks * ((rows + strip - 1) / strip);
-    if (table == kTableNone) launch<L, kTableNone, cvs::kTableL2Lanes>(im, frame, w, m, width, height, (int)strip, chunks, units, lut, most, s);
-    else if (table == kTableL2) launch<L, kTableL2, cvs::kTableL2Lanes>(im, frame, w, m, width, height, (int)strip, chunks, units, lut, most, s);
-    else launch<L, kTableLds, cvs::kTableLdsLanes>(im, frame, w, m, width, height, (int)strip, chunks, units, lut, most, s);
+    const long long chunks = ((long long)(width / 2) + kRun - 1) / kRun;
+    cvs::StripPlan p;      // strips of chroma rows
+    if (!cvs::plan_strips(chunks, height / 2, (long long)width * (long long)height, lut != nullptr, cus, kMaxStrip, &p)) return (int)hipErrorInvalidValue;
+    if (p.table == kTableNone) launch<L, kTableNone, cvs::kTableL2Lanes>(im, frame, w, m, width, height, chunks, p, lut, s);
+    else cvs::with_table(p.table, [&](auto TABLE, auto LANES) { launch<L, TABLE(), LANES()>(im, frame, w, m, width, height, chunks, p, lut, s); });
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-extern "C" int cvk_ycc420_subsample(const cvk_ycc420_image *im, cvk_view frame, cvk_rect w, int width, int height, int layout, const cvk_ycc420_encode *e,
+extern "C" int cvk_ycc420_subsample(const cvk_ycc_image *im, cvk_view frame, cvk_rect w, int width, int height, int layout, const cvk_ycc420_encode *e,
                                     const uint16_t *lut, int cus, void *stream) {
     if (width < 2 || (width & 1) || height < 2 || (height & 1)) return (int)hipErrorInvalidValue;
     if (w.x1 >= w.x0 && w.y1 >= w.y0 && (w.x0 < 0 || w.y0 < 0 || w.x1 >= width || w.y1 >= height)) return (int)hipErrorInvalidValue;
     if (e->siting < CVK_420_LEFT || e->siting > CVK_420_TOPLEFT) return (int)hipErrorInvalidValue;
-    const Coef m = { e->mat[0], e->mat[1], e->mat[2], e->mat[3], e->mat[4], e->mat[5], e->mat[6], e->mat[7], e->mat[8],
-                     e->y_scale, e->y_offset, e->c_scale, e->c_offset, e->top, e->lo, e->hi, e->siting };
+    const Coef m = { cvs::mat9(e->mat), e->y_scale, e->y_offset, e->c_scale, e->c_offset, e->top, e->lo, e->hi, e->siting };
     const long long n = cus > 0 ? cus : 256;
     hipStream_t s = (hipStream_t)stream;
     switch (layout) {

@@ -2,7 +2,7 @@
 //
 //   k_ycc420_reconstruct   no reference code; the progressive form of k_mpeg2_reconstruct (mpeg2_recon_ops.hip) with the layout a
 //                          template parameter and range, matrix and siting kernel arguments.  The contract is DESIGN.md "4:2:0
-//                          Y'CbCr edges", restated:
+//                          Y'CbCr edges", restated (decode tables, matrix, store: ycc_edge.hpp):
 //     decode     f = ((float)code - off) / div, correctly rounded; studio: off 16s / 128s, div 219s / 224s; full range: off 0 /
 //                128s, div max; s = 1, max = 255 (8-bit) or s = 4, max = 1023 (10-bit).  A 256- or 1024-entry table per kind,
 //                built in LDS by every workgroup with the same division.  PLANAR10 codes are bits 0-9, P010 codes bits 6-15
@@ -27,13 +27,12 @@
 // Algorithmic bytes per pixel: 1.5 (8-bit) or 3 (10-bit) read, 8 written.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "pixel_math.hpp"
-#include "table_placement.hpp"
+#include "ycc_edge.hpp"
 
 namespace {
 
-using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
-enum { kTableNone = 2 };
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds; using cvs::kTableNone;
+using cvs::clampi; using cvs::load_two; using cvs::Mat9;
 constexpr int kMaxStrip = 32;
 enum { kP8 = CVK_420_PLANAR8, kP10 = CVK_420_PLANAR10, kNv12 = CVK_420_NV12, kP010 = CVK_420_P010 };
 template <int L> struct Lay {
@@ -41,34 +40,17 @@ template <int L> struct Lay {
     static constexpr bool semi = L == kNv12 || L == kP010;            // Cb and Cr interleaved in plane 1
     static constexpr int codes = ten ? 1024 : 256;
 };
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// two neighbouring samples as one word: 8-bit a | b << 8, 10-bit a | b << 16 (raw: the bits that carry no code still in place)
-template <bool TEN>
-__device__ __forceinline__ uint32_t load_two(const uint8_t *p) {
-    if constexpr (TEN) {
-        if (aligned(p, 4)) return *reinterpret_cast<const uint32_t *>(p);
-        const uint16_t *q = reinterpret_cast<const uint16_t *>(p);
-        return (uint32_t)q[0] | ((uint32_t)q[1] << 16);
-    } else {
-        if (aligned(p, 2)) return *reinterpret_cast<const uint16_t *>(p);
-        return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
-    }
-}
 
 // luma columns (2k, 2k + 1) of row y
 template <int L>
-__device__ __forceinline__ uint32_t load_luma(const cvk_ycc420_image &im, int y, int k) {
+__device__ __forceinline__ uint32_t load_luma(const cvk_ycc_image &im, int y, int k) {
     constexpr int B = Lay<L>::ten ? 2 : 1;
     return load_two<Lay<L>::ten>(im.p[0] + (size_t)y * (size_t)im.stride[0] + (size_t)(2 * B) * (size_t)k);
 }
 
 // Cb and Cr of chroma row c, column k, packed like a luma pair
 template <int L>
-__device__ __forceinline__ uint32_t load_chroma(const cvk_ycc420_image &im, int c, int k) {
+__device__ __forceinline__ uint32_t load_chroma(const cvk_ycc_image &im, int c, int k) {
     constexpr int B = Lay<L>::ten ? 2 : 1;
     if constexpr (Lay<L>::semi) return load_two<Lay<L>::ten>(im.p[1] + (size_t)c * (size_t)im.stride[1] + (size_t)(2 * B) * (size_t)k);
     const uint8_t *pb = im.p[1] + (size_t)c * (size_t)im.stride[1] + (size_t)B * (size_t)k;
@@ -84,34 +66,23 @@ template <int L> __device__ __forceinline__ uint32_t second(uint32_t r) { return
 struct Raw { uint32_t y0, y1, c; };           // luma pairs of rows 2c and 2c + 1, and the chroma of row c + 1 (clamped)
 
 template <int L>
-__device__ __forceinline__ void load_pair(const cvk_ycc420_image &im, int c, int k, int ch, Raw &r) {
+__device__ __forceinline__ void load_pair(const cvk_ycc_image &im, int c, int k, int ch, Raw &r) {
     r.y0 = load_luma<L>(im, 2 * c, k);
     r.y1 = load_luma<L>(im, 2 * c + 1, k);
     r.c = load_chroma<L>(im, min(c + 1, ch - 1), k);
 }
 
 struct Coef {
-    float m0, m1, m2, m3, m4, m5, m6, m7, m8;
+    Mat9 m;
     float y_off, y_div, c_off, c_div;
     float ve_n, ve_f, vo_n, vo_f, he_n, he_f, ho_n, ho_f;
 };
-
-// one pixel: {rg, ba} codes (-ffp-contract=off: every product and sum rounds on its own)
-template <int TABLE>
-__device__ __forceinline__ uint2 pixel(float yf, float cb, float cr, const Coef &m, const uint16_t *t, uint32_t alpha) {
-    const float r = (yf * m.m0 + cb * m.m1) + cr * m.m2;
-    const float g = (yf * m.m3 + cb * m.m4) + cr * m.m5;
-    const float b = (yf * m.m6 + cb * m.m7) + cr * m.m8;
-    const uint32_t rg = cvs::f2h_rz2(r, g), bc = cvs::f2h_rz(b);
-    if constexpr (TABLE == kTableNone) return make_uint2(rg, bc | (alpha << 16));
-    else return make_uint2((uint32_t)t[rg & 0xFFFFu] | ((uint32_t)t[rg >> 16] << 16), (uint32_t)t[bc] | (alpha << 16));
-}
 
 // units: (strip of `strip` chroma rows, run of `run` chroma columns) over the window's chroma rows [ca, cb] and columns from ka;
 // `chunks` runs per strip, so the waves of neighbouring units write neighbouring parts of the same rows.  A wave's unit is
 // wave-uniform.  lead: 1 where lane 0 holds the column left of the run (centre siting), else 0; lanes lead .. lead + run - 1 write.
 template <int L, int TABLE, int LANES>
-__global__ __launch_bounds__(LANES) void k_ycc420_reconstruct(cvk_view frame, cvk_rect w, cvk_ycc420_image im, Coef m, int width, int height, int ka,
+__global__ __launch_bounds__(LANES) void k_ycc420_reconstruct(cvk_view frame, cvk_rect w, cvk_ycc_image im, Coef m, int width, int height, int ka,
                                                               int ca, int cb, int run, int lead, int strip, int chunks, int units,
                                                               const uint16_t *__restrict__ lut) {
     constexpr int kWaves = LANES / 64, N = Lay<L>::codes;
@@ -126,10 +97,7 @@ __global__ __launch_bounds__(LANES) void k_ycc420_reconstruct(cvk_view frame, cv
         load_pair<L>(im, ca + s * strip, clampi(ka + (u - s * chunks) * run + lane - lead, 0, cw - 1), ch, cur);
     }
     if (TABLE == kTableLds) cvs::stage_table<LANES>(lds, lut);      // (the wait is the __syncthreads() below)
-    for (int i = threadIdx.x; i < N; i += LANES) {
-        dec_y[i] = ((float)i - m.y_off) / m.y_div;
-        dec_c[i] = ((float)i - m.c_off) / m.c_div;
-    }
+    cvs::build_decode<N, LANES>(dec_y, dec_c, m.y_off, m.y_div, m.c_off, m.c_div);
     __syncthreads();
     uint32_t alpha = 0x3C00u;                              // f2h_rz(1.0f)
     if constexpr (TABLE != kTableNone) alpha = t[0x3C00u];
@@ -163,14 +131,10 @@ __global__ __launch_bounds__(LANES) void k_ycc420_reconstruct(cvk_view frame, cv
                 const float eb = vb * m.he_n + lb * m.he_f, er = vr * m.he_n + lr * m.he_f;
                 const float ob = vb * m.ho_n + nb * m.ho_f, orr = vr * m.ho_n + nr * m.ho_f;
                 const uint32_t luma = r ? cur.y1 : cur.y0;
-                const uint2 p0 = pixel<TABLE>(dec_y[first<L>(luma)], eb, er, m, t, alpha);
-                const uint2 p1 = pixel<TABLE>(dec_y[second<L>(luma)], ob, orr, m, t, alpha);
+                const uint2 p0 = cvs::pixel<TABLE>(dec_y[first<L>(luma)], eb, er, m.m, t, alpha);
+                const uint2 p1 = cvs::pixel<TABLE>(dec_y[second<L>(luma)], ob, orr, m.m, t, alpha);
                 uint2 *o = reinterpret_cast<uint2 *>(frame.data) + (ptrdiff_t)(y - frame.fy0) * (ptrdiff_t)frame.pitch + (x - frame.fx0);
-                if (in0 && in1 && aligned(o, 16)) __builtin_nontemporal_store(v4{ p0.x, p0.y, p1.x, p1.y }, reinterpret_cast<v4 *>(o));
-                else {
-                    if (in0) o[0] = p0;
-                    if (in1) o[1] = p1;
-                }
+                cvs::store_pixel_pair<true>(o, p0, p1, in0, in1);
             }
             ub = mb; ur = mr; mb = db; mr = dr;
             cur = nxt;
@@ -179,41 +143,35 @@ __global__ __launch_bounds__(LANES) void k_ycc420_reconstruct(cvk_view frame, cv
 }
 
 template <int L, int TABLE, int LANES>
-static void launch(cvk_view frame, cvk_rect w, const cvk_ycc420_image *im, const Coef &m, int width, int height, int ka, int ca, int cb, int run, int lead,
-                   int strip, long long chunks, long long units, const uint16_t *lut, long long most, hipStream_t s) {
-    hipLaunchKernelGGL((k_ycc420_reconstruct<L, TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, frame, w, *im, m, width, height, ka,
-                       ca, cb, run, lead, strip, (int)chunks, (int)units, lut);
+static void launch(cvk_view frame, cvk_rect w, const cvk_ycc_image *im, const Coef &m, int width, int height, int ka, int ca, int cb, int run, int lead,
+                   long long chunks, const cvs::StripPlan &p, const uint16_t *lut, hipStream_t s) {
+    hipLaunchKernelGGL((k_ycc420_reconstruct<L, TABLE, LANES>), cvs::table_grid<LANES>(p.units, p.most), dim3(LANES), 0, s, frame, w, *im, m, width, height,
+                       ka, ca, cb, run, lead, (int)p.strip, (int)chunks, (int)p.units, lut);
 }
 
-// The strip is the fewest chroma rows that leave no unit without a wave (one trip per wave where the raster allows it), as at the
-// MPEG-2 import edge.  Without a table the launch is the gathered form's: small workgroups, several per CU.
 template <int L>
-static int dispatch(cvk_view frame, cvk_rect w, const cvk_ycc420_image *im, const Coef &m, int width, int height, bool left_column, const uint16_t *lut,
+static int dispatch(cvk_view frame, cvk_rect w, const cvk_ycc_image *im, const Coef &m, int width, int height, bool left_column, const uint16_t *lut,
                     long long cus, hipStream_t s) {
     const int ka = w.x0 >> 1, ca = w.y0 >> 1, cb = w.y1 >> 1, lead = left_column ? 1 : 0, run = 63 - lead;
     const long long chunks = ((long long)(w.x1 >> 1) - ka + run) / run, rows = (long long)cb - ca + 1;
-    if (chunks * rows > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
-    // (the diagnostic build's CVS_MPEG2_TABLE: any value other than the L2 form's means LDS here)
-    const int table = !lut ? kTableNone : (cvs::table_placement((long long)width * (long long)height) == kTableL2 ? kTableL2 : kTableLds);
-    const long long lanes = table == kTableLds ? cvs::kTableLdsLanes : cvs::kTableL2Lanes;
-    const long long most = cvs::table_workgroups(table == kTableLds ? kTableLds : kTableL2, cus), waves = most * (lanes / 64);
-    long long strip = (chunks * rows + waves - 1) / waves;
-    strip = strip < 1 ? 1 : (strip > kMaxStrip ? kMaxStrip : strip);
-    const long long units = chunks * ((rows + strip - 1) / strip);
-    if (table == kTableNone) launch<L, kTableNone, cvs::kTableL2Lanes>(frame, w, im, m, width, height, ka, ca, cb, run, lead, (int)strip, chunks, units, lut, most, s);
-    else if (table == kTableL2) launch<L, kTableL2, cvs::kTableL2Lanes>(frame, w, im, m, width, height, ka, ca, cb, run, lead, (int)strip, chunks, units, lut, most, s);
-    else launch<L, kTableLds, cvs::kTableLdsLanes>(frame, w, im, m, width, height, ka, ca, cb, run, lead, (int)strip, chunks, units, lut, most, s);
+    cvs::StripPlan p;      // strips of chroma rows
+    if (!cvs::plan_strips(chunks, rows, (long long)width * (long long)height, lut != nullptr, cus, kMaxStrip, &p)) return (int)hipErrorInvalidValue;
+    if (p.table == kTableNone) launch<L, kTableNone, cvs::kTableL2Lanes>(frame, w, im, m, width, height, ka, ca, cb, run, lead, chunks, p, lut, s);
+    else
+        cvs::with_table(p.table, [&](auto TABLE, auto LANES) {
+            launch<L, TABLE(), LANES()>(frame, w, im, m, width, height, ka, ca, cb, run, lead, chunks, p, lut, s);
+        });
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-extern "C" int cvk_ycc420_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc420_image *im, int width, int height, int layout, const cvk_ycc420_decode *d,
+extern "C" int cvk_ycc420_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc_image *im, int width, int height, int layout, const cvk_ycc420_decode *d,
                                       const uint16_t *lut, int cus, void *stream) {
     if (width < 2 || (width & 1) || height < 2 || (height & 1)) return (int)hipErrorInvalidValue;
     if (w.x1 < w.x0 || w.y1 < w.y0) return 0;
     if (w.x0 < 0 || w.y0 < 0 || w.x1 >= width || w.y1 >= height) return (int)hipErrorInvalidValue;
-    const Coef m = { d->mat[0], d->mat[1], d->mat[2], d->mat[3], d->mat[4], d->mat[5], d->mat[6], d->mat[7], d->mat[8], d->y_off, d->y_div, d->c_off, d->c_div,
+    const Coef m = { cvs::mat9(d->mat), d->y_off, d->y_div, d->c_off, d->c_div,
                      d->ve[0], d->ve[1], d->vo[0], d->vo[1], d->he[0], d->he[1], d->ho[0], d->ho[1] };
     const long long n = cus > 0 ? cus : 256;
     const bool lc = d->left_column != 0;

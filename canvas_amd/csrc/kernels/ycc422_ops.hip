@@ -23,33 +23,18 @@
 // Algorithmic bytes per pixel: 8 read; 2 (PLANAR8, UYVY), 4 (PLANAR10), 2.67 (v210) written.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "pixel_math.hpp"
-#include "table_placement.hpp"
+#include "ycc_edge.hpp"
 
 namespace {
 
 using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
+using cvs::v4; using cvs::aligned; using cvs::fetch_pair; using cvs::Mat9; using cvs::Ycc; using cvs::tent;
 constexpr int kRun = 63, kMaxStrip = 64;
 enum { kP8 = CVK_422_PLANAR8, kP10 = CVK_422_PLANAR10, kUyvy = CVK_422_UYVY, kV210 = CVK_422_V210 };
 template <int L> struct Lay {
     static constexpr int pairs = L == kV210 ? 3 : 1;                          // chroma pairs (pixel pairs) per lane
     static constexpr bool ten = L == kP10 || L == kV210;
 };
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t v4a8 __attribute__((ext_vector_type(4), aligned(8)));     // a pixel pair: 8-byte aligned only
-
-__device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-// pixels (x, y) and (x + 1, y) as four dwords {rg0, ba0, rg1, ba1}; zero where a pixel is outside `w` (w lies inside the view)
-__device__ __forceinline__ v4 fetch_pair(const cvk_view &f, const cvk_rect &w, long long x, int y) {
-    v4 v = { 0u, 0u, 0u, 0u };
-    if (y < w.y0 || y > w.y1 || x + 1 < w.x0 || x > w.x1) return v;
-    const uint2 *p = reinterpret_cast<const uint2 *>(f.data) + (ptrdiff_t)(y - f.fy0) * (ptrdiff_t)f.pitch + (x - f.fx0);
-    if (x >= w.x0 && x + 1 <= w.x1) return __builtin_nontemporal_load(reinterpret_cast<const v4a8 *>(p));
-    if (x >= w.x0) { const uint2 a = p[0]; v.x = a.x; v.y = a.y; }
-    if (x + 1 <= w.x1) { const uint2 a = p[1]; v.z = a.x; v.w = a.y; }
-    return v;
-}
 
 // the P pixel pairs of lane group g of row y (a group left of the row or right of it: zeros)
 template <int P>
@@ -58,38 +43,17 @@ __device__ __forceinline__ void fetch_group(const cvk_view &f, const cvk_rect &w
     for (int i = 0; i < P; i++) px[i] = g >= 0 ? fetch_pair(f, w, 2 * ((long long)g * P + i), y) : v4{ 0u, 0u, 0u, 0u };
 }
 
-struct Mat { float m0, m1, m2, m3, m4, m5, m6, m7, m8; };
-struct Ycc { float y, cb, cr; };
-
-__device__ __forceinline__ Ycc encode(uint32_t rg, uint32_t ba, const Mat &m, const uint16_t *t) {
-    const float r = cvs::h2f(t[rg & 0xFFFFu]), g = cvs::h2f(t[rg >> 16]), b = cvs::h2f(t[ba & 0xFFFFu]);
-    Ycc o;       // -ffp-contract=off: each product and each sum rounds on its own
-    o.y = (r * m.m0 + g * m.m1) + b * m.m2;
-    o.cb = (r * m.m3 + g * m.m4) + b * m.m5;
-    o.cr = (r * m.m6 + g * m.m7) + b * m.m8;
-    return o;
-}
-
-// clamp (maxnum / minnum: NaN -> 0), scale, round half to even; the 10-bit codes 0-3 and 1020-1023 are reserved
+// studio range (cvs::quantise); the 10-bit codes 0-3 and 1020-1023 are reserved
 template <bool TEN>
-__device__ __forceinline__ uint32_t quantise(float v, bool chroma) {
+__device__ __forceinline__ uint32_t code_of(float v, bool chroma) {
     constexpr float s = TEN ? 4.0f : 1.0f, top = TEN ? 1023.0f : 255.0f;
     const float scale = chroma ? (224.0f * s) / top : (219.0f * s) / top, offset = chroma ? (128.0f * s) / top : (16.0f * s) / top;
-    const float q = v * scale + offset;
-    const uint32_t code = (uint32_t)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(q, 0.0f), 1.0f) * top);
-    return TEN ? min(max(code, 4u), 1019u) : code;
-}
-
-__device__ __forceinline__ float chroma(float left, float mid, float right) {
-    float c = 0.25f * left;
-    c = c + 0.5f * mid;
-    c = c + 0.25f * right;
-    return c;
+    return cvs::quantise(v, scale, offset, top, TEN ? 4u : 0u, TEN ? 1019u : 255u);
 }
 
 // the codes of lane group g (a pair of the row, or a v210 group whose pairs below cw are the row's) into row y of the image
 template <int L>
-__device__ __forceinline__ void store_group(const cvk_ycc422_image &im, int y, int g, int cw, const uint32_t (&yc)[2 * Lay<L>::pairs],
+__device__ __forceinline__ void store_group(const cvk_ycc_image &im, int y, int g, int cw, const uint32_t (&yc)[2 * Lay<L>::pairs],
                                             const uint32_t (&bc)[Lay<L>::pairs], const uint32_t (&rc)[Lay<L>::pairs]) {
     uint8_t *row = im.p[0] + (size_t)y * (size_t)im.stride[0];
     if constexpr (L == kV210) {
@@ -124,9 +88,7 @@ __device__ __forceinline__ void store_group(const cvk_ycc422_image &im, int y, i
         reinterpret_cast<uint16_t *>(im.p[1] + (size_t)y * (size_t)im.stride[1])[g] = (uint16_t)bc[0];
         reinterpret_cast<uint16_t *>(im.p[2] + (size_t)y * (size_t)im.stride[2])[g] = (uint16_t)rc[0];
     } else {
-        uint8_t *py = row + 2 * (size_t)g;
-        if (aligned(py, 2)) *reinterpret_cast<uint16_t *>(py) = (uint16_t)(yc[0] | (yc[1] << 8));
-        else { py[0] = (uint8_t)yc[0]; py[1] = (uint8_t)yc[1]; }
+        cvs::store_two<false>(row + 2 * (size_t)g, yc[0], yc[1]);
         (im.p[1] + (size_t)y * (size_t)im.stride[1])[g] = (uint8_t)bc[0];
         (im.p[2] + (size_t)y * (size_t)im.stride[2])[g] = (uint8_t)rc[0];
     }
@@ -134,7 +96,7 @@ __device__ __forceinline__ void store_group(const cvk_ycc422_image &im, int y, i
 
 // units: (strip of `strip` rows, run of kRun lane groups); `chunks` runs per strip.  A wave's unit is wave-uniform.
 template <int L, int TABLE, int LANES>
-__global__ __launch_bounds__(LANES) void k_ycc422_subsample(cvk_ycc422_image im, cvk_view frame, cvk_rect w, Mat m, int width, int height, int strip,
+__global__ __launch_bounds__(LANES) void k_ycc422_subsample(cvk_ycc_image im, cvk_view frame, cvk_rect w, Mat9 m, int width, int height, int strip,
                                                             int chunks, int units, const uint16_t *__restrict__ lut) {
     constexpr int kWaves = LANES / 64, P = Lay<L>::pairs;
     constexpr bool TEN = Lay<L>::ten;
@@ -165,8 +127,8 @@ __global__ __launch_bounds__(LANES) void k_ycc422_subsample(cvk_ycc422_image im,
             Ycc e[2 * P];              // columns 2 (gP + i), 2 (gP + i) + 1
 #pragma unroll
             for (int i = 0; i < P; i++) {
-                e[2 * i] = encode(px[i].x, px[i].y, m, t);
-                e[2 * i + 1] = encode(px[i].z, px[i].w, m, t);
+                e[2 * i] = cvs::encode<TABLE>(px[i].x, px[i].y, m, t);
+                e[2 * i + 1] = cvs::encode<TABLE>(px[i].z, px[i].w, m, t);
             }
 #pragma unroll
             for (int i = 0; i < P; i++) px[i] = nx[i];
@@ -177,11 +139,11 @@ __global__ __launch_bounds__(LANES) void k_ycc422_subsample(cvk_ycc422_image im,
             uint32_t yc[2 * P], bc[P], rc[P];
 #pragma unroll
             for (int i = 0; i < P; i++) {
-                yc[2 * i] = quantise<TEN>(e[2 * i].y, false);
-                yc[2 * i + 1] = quantise<TEN>(e[2 * i + 1].y, false);
+                yc[2 * i] = code_of<TEN>(e[2 * i].y, false);
+                yc[2 * i + 1] = code_of<TEN>(e[2 * i + 1].y, false);
                 const Ycc &left = e[max(2 * i - 1, 0)];        // (pair 0's left column is the neighbour lane's)
-                bc[i] = quantise<TEN>(chroma(i ? left.cb : lb, e[2 * i].cb, e[2 * i + 1].cb), true);
-                rc[i] = quantise<TEN>(chroma(i ? left.cr : lr, e[2 * i].cr, e[2 * i + 1].cr), true);
+                bc[i] = code_of<TEN>(tent(i ? left.cb : lb, e[2 * i].cb, e[2 * i + 1].cb), true);
+                rc[i] = code_of<TEN>(tent(i ? left.cr : lr, e[2 * i].cr, e[2 * i + 1].cr), true);
             }
             store_group<L>(im, y, g, cw, yc, bc, rc);
         }
@@ -189,37 +151,30 @@ __global__ __launch_bounds__(LANES) void k_ycc422_subsample(cvk_ycc422_image im,
 }
 
 template <int L, int TABLE, int LANES>
-static void launch(const cvk_ycc422_image *im, cvk_view frame, cvk_rect w, const Mat &m, int width, int height, int strip, long long chunks, long long units,
-                   const uint16_t *lut, long long most, hipStream_t s) {
-    hipLaunchKernelGGL((k_ycc422_subsample<L, TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, *im, frame, w, m, width, height, strip,
-                       (int)chunks, (int)units, lut);
+static void launch(const cvk_ycc_image *im, cvk_view frame, cvk_rect w, const Mat9 &m, int width, int height, long long chunks, const cvs::StripPlan &p,
+                   const uint16_t *lut, hipStream_t s) {
+    hipLaunchKernelGGL((k_ycc422_subsample<L, TABLE, LANES>), cvs::table_grid<LANES>(p.units, p.most), dim3(LANES), 0, s, *im, frame, w, m, width, height,
+                       (int)p.strip, (int)chunks, (int)p.units, lut);
 }
 
-// The strip is the fewest rows that leave no unit without a wave (one trip per wave where the raster allows it).
 template <int L>
-static int dispatch(const cvk_ycc422_image *im, cvk_view frame, cvk_rect w, const Mat &m, int width, int height, const uint16_t *lut, long long cus,
+static int dispatch(const cvk_ycc_image *im, cvk_view frame, cvk_rect w, const Mat9 &m, int width, int height, const uint16_t *lut, long long cus,
                     hipStream_t s) {
     constexpr int P = Lay<L>::pairs;
     const long long groups = ((long long)(width / 2) + P - 1) / P, chunks = (groups + kRun - 1) / kRun;
-    if (chunks * (long long)height > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
-    // (the diagnostic build's CVS_MPEG2_TABLE: any value other than the L2 form's means LDS here)
-    const int table = cvs::table_placement((long long)width * (long long)height) == kTableL2 ? kTableL2 : kTableLds;
-    const long long lanes = table == kTableL2 ? cvs::kTableL2Lanes : cvs::kTableLdsLanes, most = cvs::table_workgroups(table, cus), waves = most * (lanes / 64);
-    long long strip = (chunks * (long long)height + waves - 1) / waves;
-    strip = strip < 1 ? 1 : (strip > kMaxStrip ? kMaxStrip : strip);
-    const long long units = chunks * (((long long)height + strip - 1) / strip);
-    if (table == kTableL2) launch<L, kTableL2, cvs::kTableL2Lanes>(im, frame, w, m, width, height, (int)strip, chunks, units, lut, most, s);
-    else launch<L, kTableLds, cvs::kTableLdsLanes>(im, frame, w, m, width, height, (int)strip, chunks, units, lut, most, s);
+    cvs::StripPlan p;      // strips of rows
+    if (!cvs::plan_strips(chunks, height, (long long)width * (long long)height, true, cus, kMaxStrip, &p)) return (int)hipErrorInvalidValue;
+    cvs::with_table(p.table, [&](auto TABLE, auto LANES) { launch<L, TABLE(), LANES()>(im, frame, w, m, width, height, chunks, p, lut, s); });
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-extern "C" int cvk_ycc422_subsample(const cvk_ycc422_image *im, cvk_view frame, cvk_rect w, int width, int height, int layout, const float mat[9],
+extern "C" int cvk_ycc422_subsample(const cvk_ycc_image *im, cvk_view frame, cvk_rect w, int width, int height, int layout, const float mat[9],
                                     const uint16_t *lut, int cus, void *stream) {
     if (width < 2 || (width & 1) || height < 1) return (int)hipErrorInvalidValue;
     if (w.x1 >= w.x0 && w.y1 >= w.y0 && (w.x0 < 0 || w.y0 < 0 || w.x1 >= width || w.y1 >= height)) return (int)hipErrorInvalidValue;
-    const Mat m = { mat[0], mat[1], mat[2], mat[3], mat[4], mat[5], mat[6], mat[7], mat[8] };
+    const Mat9 m = cvs::mat9(mat);
     const long long n = cus > 0 ? cus : 256;
     hipStream_t s = (hipStream_t)stream;
     switch (layout) {

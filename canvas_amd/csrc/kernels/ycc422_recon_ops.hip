@@ -24,12 +24,11 @@
 // Algorithmic bytes read per pixel: 2 (PLANAR8, UYVY), 4 (PLANAR10), 2.67 (v210); 8 written.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "pixel_math.hpp"
-#include "table_placement.hpp"
+#include "ycc_edge.hpp"
 
 namespace {
 
-using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds;
+using cvs::kTable; using cvs::kTableL2; using cvs::kTableLds; using cvs::v4; using cvs::aligned; using cvs::Mat9;
 constexpr int kRun = 63, kMaxStrip = 64;
 enum { kP8 = CVK_422_PLANAR8, kP10 = CVK_422_PLANAR10, kUyvy = CVK_422_UYVY, kV210 = CVK_422_V210 };
 template <int L> struct Lay {
@@ -37,16 +36,13 @@ template <int L> struct Lay {
     static constexpr int codes = L == kP10 || L == kV210 ? 1024 : 256;        // sample codes
     static constexpr int words = L == kV210 ? 4 : (L == kP10 ? 2 : 1);        // dwords a lane's samples make
 };
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 // The samples of lane group g of row y as dwords:
 //   PLANAR8   r[0] = Y'0 | Y'1 << 8 | Cb << 16 | Cr << 24      PLANAR10  r[0] = Y'0 | Y'1 << 16, r[1] = Cb | Cr << 16
 //   UYVY      r[0] = Cb | Y'0 << 8 | Cr << 16 | Y'1 << 24      V210      the group's four words
 // each read at the pair (the group) clamped to the row's last.
 template <int L>
-__device__ __forceinline__ void load_raw(const cvk_ycc422_image &im, int y, int g, int cw, uint32_t (&r)[Lay<L>::words]) {
+__device__ __forceinline__ void load_raw(const cvk_ycc_image &im, int y, int g, int cw, uint32_t (&r)[Lay<L>::words]) {
     const uint8_t *row = im.p[0] + (size_t)y * (size_t)im.stride[0];
     if constexpr (L == kV210) {
         const uint8_t *p = row + (size_t)min(g, (cw + 2) / 3 - 1) * 16;
@@ -69,9 +65,7 @@ __device__ __forceinline__ void load_raw(const cvk_ycc422_image &im, int y, int 
             r[0] = aligned(py, 4) ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(py)) : ((uint32_t)py[0] | ((uint32_t)py[1] << 16));
             r[1] = (uint32_t)reinterpret_cast<const uint16_t *>(rb)[k] | ((uint32_t)reinterpret_cast<const uint16_t *>(rr)[k] << 16);
         } else {
-            const uint8_t *py = row + 2 * k;
-            const uint32_t luma = aligned(py, 2) ? *reinterpret_cast<const uint16_t *>(py) : ((uint32_t)py[0] | ((uint32_t)py[1] << 8));
-            r[0] = luma | ((uint32_t)rb[k] << 16) | ((uint32_t)rr[k] << 24);
+            r[0] = cvs::load_two<false>(row + 2 * k) | ((uint32_t)rb[k] << 16) | ((uint32_t)rr[k] << 24);
         }
     }
 }
@@ -109,21 +103,10 @@ __device__ __forceinline__ void decode(const uint32_t (&r)[Lay<L>::words], int g
     }
 }
 
-struct Mat { float m0, m1, m2, m3, m4, m5, m6, m7, m8; };
-
-// one pixel: {rg, ba} codes after the table (-ffp-contract=off: every product and sum rounds on its own)
-__device__ __forceinline__ uint2 pixel(float yf, float cb, float cr, const Mat &m, const uint16_t *t, uint32_t alpha) {
-    const float r = (yf * m.m0 + cb * m.m1) + cr * m.m2;
-    const float g = (yf * m.m3 + cb * m.m4) + cr * m.m5;
-    const float b = (yf * m.m6 + cb * m.m7) + cr * m.m8;
-    const uint32_t rg = cvs::f2h_rz2(r, g), bc = cvs::f2h_rz(b);
-    return make_uint2((uint32_t)t[rg & 0xFFFFu] | ((uint32_t)t[rg >> 16] << 16), (uint32_t)t[bc] | (alpha << 16));
-}
-
 // units: (strip of `strip` rows, run of kRun lane groups) over the window's rows [w.y0, w.y1] and groups from ga; `chunks` runs per
 // strip, so the waves of neighbouring units write neighbouring parts of the same rows.  A wave's unit is wave-uniform.
 template <int L, int TABLE, int LANES>
-__global__ __launch_bounds__(LANES) void k_ycc422_reconstruct(cvk_view frame, cvk_rect w, cvk_ycc422_image im, Mat m, int width, int ga, int strip,
+__global__ __launch_bounds__(LANES) void k_ycc422_reconstruct(cvk_view frame, cvk_rect w, cvk_ycc_image im, Mat9 m, int width, int ga, int strip,
                                                               int chunks, int units, const uint16_t *__restrict__ lut) {
     constexpr int kWaves = LANES / 64, P = Lay<L>::pairs, N = Lay<L>::codes, NW = Lay<L>::words;
     constexpr float s = N / 256;
@@ -140,10 +123,7 @@ __global__ __launch_bounds__(LANES) void k_ycc422_reconstruct(cvk_view frame, cv
         load_raw<L>(im, w.y0 + sr * strip, ga + (u - sr * chunks) * kRun + lane, cw, cur);
     }
     if (TABLE == kTableLds) cvs::stage_table<LANES>(lds, lut);      // (the wait is the __syncthreads() below)
-    for (int i = threadIdx.x; i < N; i += LANES) {
-        dec_y[i] = ((float)i - 16.0f * s) / (219.0f * s);
-        dec_c[i] = ((float)i - 128.0f * s) / (224.0f * s);
-    }
+    cvs::build_decode<N, LANES>(dec_y, dec_c, 16.0f * s, 219.0f * s, 128.0f * s, 224.0f * s);
     __syncthreads();
     const uint32_t alpha = t[0x3C00u];                     // f2h_rz(1.0f)
     for (bool first = true; u < units; u += stride, first = false) {
@@ -165,19 +145,12 @@ __global__ __launch_bounds__(LANES) void k_ycc422_reconstruct(cvk_view frame, cv
                 const long long x = 2 * ((long long)g * P + i);
                 const float vb = cb[i], vr = cr[i], vb1 = i < kLast ? cb[min(i + 1, kLast)] : nb, vr1 = i < kLast ? cr[min(i + 1, kLast)] : nr;
                 const float hb = (vb + vb1) * 0.5f, hr = (vr + vr1) * 0.5f;
-                const uint2 p0 = pixel(yf[2 * i], vb, vr, m, t, alpha);
-                const uint2 p1 = pixel(yf[2 * i + 1], hb, hr, m, t, alpha);
+                const uint2 p0 = cvs::pixel<TABLE>(yf[2 * i], vb, vr, m, t, alpha);
+                const uint2 p1 = cvs::pixel<TABLE>(yf[2 * i + 1], hb, hr, m, t, alpha);
                 const bool in0 = lane < kRun && x >= w.x0 && x <= w.x1, in1 = lane < kRun && x + 1 >= w.x0 && x + 1 <= w.x1;
-                uint2 *q = o + (x - frame.fx0);
                 // non-temporal where neighbouring lanes write neighbouring pairs; a v210 lane's three pairs lie 48 bytes from its
                 // neighbour's, and plain stores let L2 put the lines together before they leave
-                if (in0 && in1 && aligned(q, 16)) {
-                    if (P == 1) __builtin_nontemporal_store(v4{ p0.x, p0.y, p1.x, p1.y }, reinterpret_cast<v4 *>(q));
-                    else *reinterpret_cast<v4 *>(q) = v4{ p0.x, p0.y, p1.x, p1.y };
-                } else {
-                    if (in0) q[0] = p0;
-                    if (in1) q[1] = p1;
-                }
+                cvs::store_pixel_pair<P == 1>(o + (x - frame.fx0), p0, p1, in0, in1);
             }
 #pragma unroll
             for (int i = 0; i < NW; i++) cur[i] = nxt[i];
@@ -186,40 +159,32 @@ __global__ __launch_bounds__(LANES) void k_ycc422_reconstruct(cvk_view frame, cv
 }
 
 template <int L, int TABLE, int LANES>
-static void launch(cvk_view frame, cvk_rect w, const cvk_ycc422_image *im, const Mat &m, int width, int ga, int strip, long long chunks, long long units,
-                   const uint16_t *lut, long long most, hipStream_t s) {
-    hipLaunchKernelGGL((k_ycc422_reconstruct<L, TABLE, LANES>), cvs::table_grid<LANES>(units, most), dim3(LANES), 0, s, frame, w, *im, m, width, ga, strip,
-                       (int)chunks, (int)units, lut);
+static void launch(cvk_view frame, cvk_rect w, const cvk_ycc_image *im, const Mat9 &m, int width, int ga, long long chunks, const cvs::StripPlan &p,
+                   const uint16_t *lut, hipStream_t s) {
+    hipLaunchKernelGGL((k_ycc422_reconstruct<L, TABLE, LANES>), cvs::table_grid<LANES>(p.units, p.most), dim3(LANES), 0, s, frame, w, *im, m, width, ga,
+                       (int)p.strip, (int)chunks, (int)p.units, lut);
 }
 
-// The strip is the fewest rows that leave no unit without a wave (one trip per wave where the raster allows it), as at the MPEG-2
-// import edge.
 template <int L>
-static int dispatch(cvk_view frame, cvk_rect w, const cvk_ycc422_image *im, const Mat &m, int width, int height, const uint16_t *lut, long long cus,
+static int dispatch(cvk_view frame, cvk_rect w, const cvk_ycc_image *im, const Mat9 &m, int width, int height, const uint16_t *lut, long long cus,
                     hipStream_t s) {
     constexpr int P = Lay<L>::pairs;
     const int ga = w.x0 / (2 * P);
     const long long chunks = ((long long)(w.x1 / (2 * P)) - ga + kRun) / kRun, rows = (long long)w.y1 - w.y0 + 1;
-    if (chunks * rows > 0x7FFFFFFFLL - (1LL << 20)) return (int)hipErrorInvalidValue;
-    // (the diagnostic build's CVS_MPEG2_TABLE: any value other than the L2 form's means LDS here)
-    const int table = cvs::table_placement((long long)width * (long long)height) == kTableL2 ? kTableL2 : kTableLds;
-    const long long lanes = table == kTableL2 ? cvs::kTableL2Lanes : cvs::kTableLdsLanes, most = cvs::table_workgroups(table, cus), waves = most * (lanes / 64);
-    long long strip = (chunks * rows + waves - 1) / waves;
-    strip = strip < 1 ? 1 : (strip > kMaxStrip ? kMaxStrip : strip);
-    const long long units = chunks * ((rows + strip - 1) / strip);
-    if (table == kTableL2) launch<L, kTableL2, cvs::kTableL2Lanes>(frame, w, im, m, width, ga, (int)strip, chunks, units, lut, most, s);
-    else launch<L, kTableLds, cvs::kTableLdsLanes>(frame, w, im, m, width, ga, (int)strip, chunks, units, lut, most, s);
+    cvs::StripPlan p;      // strips of rows
+    if (!cvs::plan_strips(chunks, rows, (long long)width * (long long)height, true, cus, kMaxStrip, &p)) return (int)hipErrorInvalidValue;
+    cvs::with_table(p.table, [&](auto TABLE, auto LANES) { launch<L, TABLE(), LANES()>(frame, w, im, m, width, ga, chunks, p, lut, s); });
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-extern "C" int cvk_ycc422_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc422_image *im, int width, int height, int layout, const float mat[9],
+extern "C" int cvk_ycc422_reconstruct(cvk_view frame, cvk_rect w, const cvk_ycc_image *im, int width, int height, int layout, const float mat[9],
                                       const uint16_t *lut, int cus, void *stream) {
     if (width < 2 || (width & 1) || height < 1) return (int)hipErrorInvalidValue;
     if (w.x1 < w.x0 || w.y1 < w.y0) return 0;
     if (w.x0 < 0 || w.y0 < 0 || w.x1 >= width || w.y1 >= height) return (int)hipErrorInvalidValue;
-    const Mat m = { mat[0], mat[1], mat[2], mat[3], mat[4], mat[5], mat[6], mat[7], mat[8] };
+    const Mat9 m = cvs::mat9(mat);
     const long long n = cus > 0 ? cus : 256;
     hipStream_t s = (hipStream_t)stream;
     switch (layout) {

@@ -55,6 +55,11 @@ PyObject *pyext_capsule_getter(PyObject *self, void *closure);      /* closure =
 int pyext_add_type(PyObject *module, const char *name, PyTypeObject *type);
 int pyext_make_capsule(PyObject **slot, video_frame_source_funcs *funcs);
 
+/* a keyword that names one of a few values: the table ends with a NULL name.  *value = the value of `given` (absent: `def`); false
+ * with a ValueError that names the choices, as in: Node: layout must be "planar8", "planar10", "uyvy" or "v210", not 'x' */
+typedef struct { const char *name; int value; } pyext_choice;
+bool pyext_choose(const char *node, const char *what, PyObject *given, const pyext_choice *choices, int def, int *value);
+
 /* a node with one upstream source (pysources.c): the struct every such type starts with, the `source` attribute's getter and
  * setter and the set_source(source) method table; reader lock around any upstream pull, writer lock where the source changes */
 typedef struct { PyObject_HEAD pthread_rwlock_t lock; video_source *source; } node1;

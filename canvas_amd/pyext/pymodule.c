@@ -45,6 +45,20 @@ CVS_EXPORT bool py_parse_box2i(PyObject *o, box2i *b) { return PyArg_ParseTuple(
 CVS_EXPORT bool py_parse_box2f(PyObject *o, box2f *b) { return PyArg_ParseTuple(o, "(ff)(ff)", &b->min.x, &b->min.y, &b->max.x, &b->max.y) != 0; }
 CVS_EXPORT bool py_parse_rgba_f32(PyObject *o, rgba_f32 *c) { return PyArg_ParseTuple(o, "ffff", &c->r, &c->g, &c->b, &c->a) != 0; }
 
+bool pyext_choose(const char *node, const char *what, PyObject *given, const pyext_choice *choices, int def, int *value) {
+    *value = def;
+    if (!given) return true;
+    const char *s = PyUnicode_Check(given) ? PyUnicode_AsUTF8(given) : NULL;
+    for (const pyext_choice *c = choices; s && c->name; c++)
+        if (!strcmp(s, c->name)) { *value = c->value; return true; }
+    char names[128] = "";
+    for (const pyext_choice *c = choices; c->name; c++)
+        snprintf(names + strlen(names), sizeof names - strlen(names), "%s\"%s\"", c == choices ? "" : (c[1].name ? ", " : " or "), c->name);
+    PyErr_Clear();
+    PyErr_Format(PyExc_ValueError, "%s: %s must be %s, not %R", node, what, names, given);
+    return false;
+}
+
 CVS_EXPORT bool py_parse_rational(PyObject *in, rational *out) {
     if (PyLong_Check(in)) { out->n = (int32_t)PyLong_AsLong(in); out->d = 1; return !PyErr_Occurred(); }
     PyObject *n = PyObject_GetAttrString(in, "numerator"), *d = n ? PyObject_GetAttrString(in, "denominator") : NULL;

@@ -15,28 +15,11 @@
 #include "canvas_ycc420.h"
 
 typedef struct { int width, height, layout, flags, planes; } ycc420_args;
-typedef struct { const char *name; int value; } choice;
-
-static const choice layouts[] = { { "planar8", CVS_420_PLANAR8 }, { "planar10", CVS_420_PLANAR10 }, { "nv12", CVS_420_NV12 }, { "p010", CVS_420_P010 }, { NULL, 0 } };
-static const choice matrices[] = { { "601", 0 }, { "709", CVS_YCC_REC709 }, { "2020", CVS_YCC_REC2020 }, { NULL, 0 } };
-static const choice ranges[] = { { "studio", 0 }, { "full", CVS_YCC_FULL_RANGE }, { NULL, 0 } };
-static const choice sitings[] = { { "left", 0 }, { "center", CVS_YCC_SITING_CENTER }, { "topleft", CVS_YCC_SITING_TOPLEFT }, { NULL, 0 } };
-static const choice transfers[] = { { "709", 0 }, { "none", CVS_YCC_NO_TRANSFER }, { NULL, 0 } };
-
-/* the value of keyword `what` (absent: `def`); false with a ValueError that names the choices */
-static bool choose(const char *node, const char *what, PyObject *given, const choice *choices, int def, int *value) {
-    *value = def;
-    if (!given) return true;
-    const char *s = PyUnicode_Check(given) ? PyUnicode_AsUTF8(given) : NULL;
-    for (const choice *c = choices; s && c->name; c++)
-        if (!strcmp(s, c->name)) { *value = c->value; return true; }
-    char names[128] = "";
-    for (const choice *c = choices; c->name; c++)
-        snprintf(names + strlen(names), sizeof names - strlen(names), "%s\"%s\"", c == choices ? "" : (c[1].name ? ", " : " or "), c->name);
-    PyErr_Clear();
-    PyErr_Format(PyExc_ValueError, "%s: %s must be %s, not %R", node, what, names, given);
-    return false;
-}
+static const pyext_choice layouts[] = { { "planar8", CVS_420_PLANAR8 }, { "planar10", CVS_420_PLANAR10 }, { "nv12", CVS_420_NV12 }, { "p010", CVS_420_P010 }, { NULL, 0 } };
+static const pyext_choice matrices[] = { { "601", 0 }, { "709", CVS_YCC_REC709 }, { "2020", CVS_YCC_REC2020 }, { NULL, 0 } };
+static const pyext_choice ranges[] = { { "studio", 0 }, { "full", CVS_YCC_FULL_RANGE }, { NULL, 0 } };
+static const pyext_choice sitings[] = { { "left", 0 }, { "center", CVS_YCC_SITING_CENTER }, { "topleft", CVS_YCC_SITING_TOPLEFT }, { NULL, 0 } };
+static const pyext_choice transfers[] = { { "709", 0 }, { "none", CVS_YCC_NO_TRANSFER }, { NULL, 0 } };
 
 /* size and the five keywords as both nodes take them; false with a ValueError (or the parser's error) set */
 static bool args_parse(const char *node, PyObject *args, PyObject *kw, PyObject **src, ycc420_args *a) {
@@ -46,8 +29,9 @@ static bool args_parse(const char *node, PyObject *args, PyObject *kw, PyObject 
     v2i sz;
     if (!py_parse_v2i(size, &sz)) return false;
     int m, r, s, t;
-    if (!choose(node, "layout", layout, layouts, CVS_420_NV12, &a->layout) || !choose(node, "matrix", matrix, matrices, CVS_YCC_REC709, &m) ||
-        !choose(node, "range", range, ranges, 0, &r) || !choose(node, "siting", siting, sitings, 0, &s) || !choose(node, "transfer", transfer, transfers, 0, &t))
+    if (!pyext_choose(node, "layout", layout, layouts, CVS_420_NV12, &a->layout) || !pyext_choose(node, "matrix", matrix, matrices, CVS_YCC_REC709, &m) ||
+        !pyext_choose(node, "range", range, ranges, 0, &r) || !pyext_choose(node, "siting", siting, sitings, 0, &s) ||
+        !pyext_choose(node, "transfer", transfer, transfers, 0, &t))
         return false;
     a->flags = m | r | s | t;
     int strides[3], lines[3];

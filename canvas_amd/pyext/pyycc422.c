@@ -13,34 +13,18 @@
 
 typedef struct { int width, height, layout, flags, planes; } ycc422_args;
 
-static const char *const layout_names[] = { "planar8", "planar10", "uyvy", "v210" };
+static const pyext_choice layouts[] = { { "planar8", CVS_422_PLANAR8 }, { "planar10", CVS_422_PLANAR10 }, { "uyvy", CVS_422_UYVY }, { "v210", CVS_422_V210 }, { NULL, 0 } };
+static const pyext_choice matrices[] = { { "601", 0 }, { "709", CVS_YCC_REC709 }, { NULL, 0 } };
 
-/* size, layout and matrix as both nodes take them; false with a ValueError (or the parser's error) set */
-static bool args_parse(const char *node, PyObject *size, PyObject *layout, PyObject *matrix, ycc422_args *a) {
+/* size and the two keywords as both nodes take them; false with a ValueError (or the parser's error) set */
+static bool args_parse(const char *node, PyObject *args, PyObject *kw, PyObject **src, ycc422_args *a) {
+    static char *kwlist[] = { "source", "size", "layout", "matrix", NULL };
+    PyObject *size, *layout = NULL, *matrix = NULL;
+    if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|OO", kwlist, src, &size, &layout, &matrix)) return false;
     v2i sz;
     if (!py_parse_v2i(size, &sz)) return false;
-    a->layout = CVS_422_V210;
-    a->flags = CVS_YCC_REC709;
-    if (layout) {
-        const char *l = PyUnicode_Check(layout) ? PyUnicode_AsUTF8(layout) : NULL;
-        a->layout = -1;
-        for (int i = 0; l && i < 4; i++)
-            if (!strcmp(l, layout_names[i])) a->layout = i;
-        if (a->layout < 0) {
-            PyErr_Clear();
-            PyErr_Format(PyExc_ValueError, "%s: layout must be \"planar8\", \"planar10\", \"uyvy\" or \"v210\", not %R", node, layout);
-            return false;
-        }
-    }
-    if (matrix) {
-        const char *m = PyUnicode_Check(matrix) ? PyUnicode_AsUTF8(matrix) : NULL;
-        if (m && !strcmp(m, "601")) a->flags = 0;
-        else if (!m || strcmp(m, "709")) {
-            PyErr_Clear();
-            PyErr_Format(PyExc_ValueError, "%s: matrix must be \"601\" or \"709\", not %R", node, matrix);
-            return false;
-        }
-    }
+    if (!pyext_choose(node, "layout", layout, layouts, CVS_422_V210, &a->layout) || !pyext_choose(node, "matrix", matrix, matrices, CVS_YCC_REC709, &a->flags))
+        return false;
     int strides[3], lines[3];
     a->planes = cvs_ycc422_layout(a->layout, sz.x, sz.y, strides, lines);
     if (a->planes < 0) {
@@ -57,11 +41,9 @@ static bool args_parse(const char *node, PyObject *size, PyObject *layout, PyObj
 typedef struct { PyObject_HEAD CodedImageSourceHolder source; ycc422_args a; } py_ycc422recon;
 
 static int recon_init(py_ycc422recon *self, PyObject *args, PyObject *kw) {
-    static char *kwlist[] = { "source", "size", "layout", "matrix", NULL };
-    PyObject *src, *size, *layout = NULL, *matrix = NULL;
-    if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|OO", kwlist, &src, &size, &layout, &matrix)) return -1;
+    PyObject *src;
     ycc422_args a;
-    if (!args_parse("YCbCr422ReconstructionFilter", size, layout, matrix, &a)) return -1;
+    if (!args_parse("YCbCr422ReconstructionFilter", args, kw, &src, &a)) return -1;
     if (!py_coded_image_take_source(src, &self->source)) return -1;
     self->a = a;
     return 0;
@@ -93,11 +75,9 @@ static PyTypeObject py_type_YCbCr422ReconstructionFilter = {
 typedef struct { PyObject_HEAD video_source *source; ycc422_args a; } py_ycc422sub;
 
 static int sub_init(py_ycc422sub *self, PyObject *args, PyObject *kw) {
-    static char *kwlist[] = { "source", "size", "layout", "matrix", NULL };
-    PyObject *src, *size, *layout = NULL, *matrix = NULL;
-    if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|OO", kwlist, &src, &size, &layout, &matrix)) return -1;
+    PyObject *src;
     ycc422_args a;
-    if (!args_parse("YCbCr422SubsampleFilter", size, layout, matrix, &a)) return -1;
+    if (!args_parse("YCbCr422SubsampleFilter", args, kw, &src, &a)) return -1;
     if (!py_video_take_source(src, &self->source)) return -1;
     self->a = a;
     return 0;

@@ -1,5 +1,6 @@
 """The 4:2:2 Y'CbCr edges without a GPU (DESIGN.md "4:2:2 Y'CbCr edges"): include/canvas_ycc422.h against the library and its
-bindings; cvs_ycc422_layout, which is host only; the numpy model (tests/ycc422_model.py) pinned against studio-range anchors,
+bindings; cvs_ycc422_layout, which is host only; every argument refusal of the two device entries by its message (they come before
+the device is touched); the numpy model (tests/ycc422_model.py) pinned against studio-range anchors,
 its pack and unpack functions against each other, a float64 restatement, the MPEG-2 edges' models and the round-trip facts; the
 catalogue of tests/ycc422_cases.py, which must exercise every rule of the contract; the built code objects; the nodes' arguments."""
 import ctypes as C
@@ -126,6 +127,84 @@ def test_without_a_gpu_the_device_entries_refuse_or_fail_loudly(lib):
     assert lib.cvs_reconstruct_422_dev(None, C.byref(img), 8, 8, 3, 0, None) == -1
     assert lib.cvs_subsample_422_dev(C.byref(img), frame.ref(), 8, 8, 3, 1, None) == -1        # CVS_YCC_PROGRESSIVE: no such thing here
     assert lib.cvs_subsample_422_dev(C.byref(img), None, 8, 8, 3, 0, None) == -1
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_every_argument_refusal_by_its_message_and_nothing_is_written(lib, layout):
+    """The refusals of tests/test_ycc422_gpu.py with no device: each comes before the device is touched, as the 4:2:0 edges' do, so
+    host memory stands in for the operands and is seen to stay as it was."""
+    from canvas_amd import _lib
+    from canvas_amd.abi import HostFrame
+    from tests.entry_cases import SENT16
+    width, height, lid = 24, 4, ym.LAYOUTS[layout]
+    full = (0, 0, width - 1, height - 1)
+    strides, lines = ym.least(layout, width, height)
+    arrays = [np.full(s * n + 64, 0xA5, np.uint8) for s, n in zip(strides, lines)]
+    assert all(a.ctypes.data % 16 == 0 for a in arrays)            # (numpy's allocations are aligned well beyond 4)
+    before = np.broadcast_to(SENT16, (height, width, 4)).copy()
+    frame = HostFrame(full, np.uint16, before.copy(), full)
+
+    def image(count=len(arrays)):
+        img = _lib.coded_image()
+        for p, (a, s, n) in enumerate(list(zip(arrays, strides, lines))[:count]):
+            img.data[p], img.stride[p], img.line_count[p] = a.ctypes.data, s, n
+        return img
+
+    def refused(img, w, h, lay, flags, word, fr=frame):
+        for entry in ("reconstruct", "subsample"):
+            if fr is not None:
+                fr.c.current_window = _lib.box2i.of(*full)
+            lib.cvs_clear_last_error()
+            ref = fr.ref() if fr is not None else None
+            if entry == "reconstruct":
+                rc = lib.cvs_reconstruct_422_dev(ref, C.byref(img) if img is not None else None, w, h, lay, flags, None)
+                assert fr is None or fr.current_window.is_empty(), (entry, word)
+            else:
+                rc = lib.cvs_subsample_422_dev(C.byref(img) if img is not None else None, ref, w, h, lay, flags, None)
+            assert rc == -1 and word in _lib.last_error(), (entry, word, rc, _lib.last_error())
+            assert "4:2:2 " + entry in _lib.last_error(), _lib.last_error()
+
+    refused(image(), width, height, lid, 0, "need a frame", fr=None)
+    for w in (23, 25, 1, 0, -2):
+        refused(image(), w, height, lid, 0, "width")
+    for h in (0, -1):
+        refused(image(), width, h, lid, 0, "height")
+    for flags in (_lib.YCC_PROGRESSIVE, _lib.YCC_PROGRESSIVE | _lib.YCC_REC709, 4, -1):
+        refused(image(), width, height, lid, flags, "unknown flags")
+    for lay in (-1, 4, 17):
+        refused(image(), width, height, lay, 0, "unknown layout")
+    refused(None, width, height, lid, 0, "need an image")
+    for p in range(len(arrays)):
+        img = image()
+        img.data[p] = None
+        refused(img, width, height, lid, 0, "plane %d is missing" % p)
+        img = image()
+        img.stride[p] -= ym.ALIGN[layout]
+        refused(img, width, height, lid, 0, "too short")
+        img = image()
+        img.line_count[p] -= 1
+        refused(img, width, height, lid, 0, "too short")
+        for off in range(1, ym.ALIGN[layout]):
+            if ym.ALIGN[layout] % off == 0:                            # 1, and 2 where the alignment is 4
+                img = image()
+                img.data[p] = arrays[p].ctypes.data + off
+                refused(img, width, height, lid, 0, "misaligned")
+        if ym.ALIGN[layout] > 1:
+            img = image()
+            img.stride[p] += 1
+            refused(img, width, height, lid, 0, "misaligned")
+    if len(arrays) == 3:                        # a planar layout handed one plane: too few planes
+        refused(image(1), width, height, lid, 0, "takes 3 planes, plane 1 is missing")
+    else:
+        img = image()
+        img.data[0] = None
+        refused(img, width, height, lid, 0, "takes 1 plane, plane 0 is missing")
+    # a current window outside the buffer (export only reads it)
+    frame.c.current_window = _lib.box2i.of(0, 0, width, height - 1)
+    lib.cvs_clear_last_error()
+    assert lib.cvs_subsample_422_dev(C.byref(image()), frame.ref(), width, height, lid, 0, None) == -1 and "outside the buffer" in _lib.last_error()
+    assert all((a == 0xA5).all() for a in arrays), "a refused call wrote a plane"
+    assert np.array_equal(frame.array, before), "a refused call wrote the frame"
 
 
 # ---------------------------------------------------------------- the model: layouts

@@ -30,7 +30,7 @@ from canvas_amd.device import DeviceFrame  # noqa: E402
 SIZES = [(720, 480), (1920, 1080), (3840, 2160)]
 PEAK = 8.0e12
 ROTATE_BYTES = 512 << 20
-TABLES = {"lds": 0, "l2": 1, "lds_unstaged": 2}             # kernels/mpeg2_ops.hip kTable*
+TABLES = {"lds": 0, "l2": 1, "lds_unstaged": 3}             # kernels/table_placement.hpp kTable*
 
 
 def time_reconstruct(lib, stream, e0, e1, args, w, h):
