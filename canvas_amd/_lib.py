@@ -1,7 +1,7 @@
 """ctypes binding of libcanvas_hip.so (the C-ABI declared in include/canvas_hip.h and, for the scopes, the 3D LUT, the corner pin
 the adaptive deinterlacer, the median and the temporal denoise, include/canvas_scope.h, include/canvas_lut3d.h,
 include/canvas_perspective.h, include/canvas_deinterlace.h, include/canvas_median.h, include/canvas_temporal.h,
-include/canvas_ycc422.h, include/canvas_ycc420.h and include/canvas_primary.h).
+include/canvas_ycc422.h, include/canvas_ycc420.h, include/canvas_primary.h and include/canvas_secondary.h).
 
 There is no fallback: if the shared library is missing or cannot be loaded, importing symbols
 from here raises, and every pixel entry point needs a HIP device at run time.
@@ -29,6 +29,8 @@ SCOPE_HISTOGRAM, SCOPE_WAVEFORM, SCOPE_PARADE, SCOPE_VECTORSCOPE = range(4)     
 SCOPE_SKIP_TRANSPARENT, SCOPE_MAX_COLUMNS = 1, 4096                             # cvs_scope.flags and the limit of its columns
 LUT3D_MIN_SIZE, LUT3D_MAX_SIZE = 2, 65                                           # cvs_lut3d.size
 CURVES_MIN_SIZE, CURVES_MAX_SIZE, PRIMARY_MATRIX = 2, 4097, 1                    # cvs_curves.size, cvs_primary.flags
+QUAL_HUE, QUAL_SATURATION, QUAL_LUMA, QUAL_INVERT, QUAL_SHOW_MATTE = 1, 2, 4, 8, 16                   # cvs_qualifier.flags
+MMIX_LUMA, MMIX_INVERT = 1, 2                                                    # cvs_matte_mix.flags
 PERSPECTIVE_MAX_SPAN = 1 << 23                                                   # cvs_perspective: how far a window may lie from its origin
 YCC_PROGRESSIVE, YCC_REC709 = 1, 2                  # cvs_reconstruct_mpeg2_dev flags (0: interlaced siting, Rec.601)
 
@@ -119,6 +121,39 @@ def primary(pre=None, matrix=None, post=None, flags=None):
     if len(m) != 12:
         raise ValueError("matrix takes 12 numbers, three rows of four")
     return primary_params(stage(pre), (C.c_float * 12)(*m), stage(post), int((PRIMARY_MATRIX if matrix is not None else 0) if flags is None else flags))
+
+
+class hue_range(C.Structure):
+    _fields_ = [("center", C.c_float), ("width", C.c_float), ("softness", C.c_float)]
+
+
+class value_range(C.Structure):
+    _fields_ = [("low", C.c_float), ("high", C.c_float), ("soft_low", C.c_float), ("soft_high", C.c_float)]
+
+
+class qualifier_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("hue", hue_range), ("saturation", value_range), ("luma", value_range)]
+
+
+class matte_mix_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32)]
+
+
+def qualifier(hue=None, saturation=None, luma=None, invert=False, show_matte=False, flags=None):
+    """A cvs_qualifier for the two cvs_qualify entries.  hue: None (the axis does not qualify) or (center, width, softness) in
+    degrees; saturation / luma: None or (low, high, soft_low, soft_high).  flags: the axes given, invert and show_matte, unless
+    stated."""
+    f = (QUAL_HUE if hue is not None else 0) | (QUAL_SATURATION if saturation is not None else 0) | (QUAL_LUMA if luma is not None else 0)
+    f |= (QUAL_INVERT if invert else 0) | (QUAL_SHOW_MATTE if show_matte else 0)
+    h = hue_range(*[float(v) for v in hue]) if hue is not None else hue_range()
+    s = value_range(*[float(v) for v in saturation]) if saturation is not None else value_range()
+    y = value_range(*[float(v) for v in luma]) if luma is not None else value_range()
+    return qualifier_params(int(f if flags is None else flags) & 0xFFFFFFFF, h, s, y)
+
+
+def matte_mix(luma=False, invert=False, flags=None):
+    """A cvs_matte_mix for the two cvs_matte_mix entries: k from the matte's alpha, or from its Rec.709 luma; inverted or not."""
+    return matte_mix_params(int(((MMIX_LUMA if luma else 0) | (MMIX_INVERT if invert else 0)) if flags is None else flags) & 0xFFFFFFFF)
 
 
 class perspective_params(C.Structure):
@@ -359,6 +394,14 @@ PRIMARY_SIGNATURES = {
     "cvs_primary_f32_dev": (C.c_int, [_F32, _F32, P(primary_params), _vp, _vp, _vp]),
 }
 
+# the same for include/canvas_secondary.h (secondaries: the HSL qualifier and the mix through a matte)
+SECONDARY_SIGNATURES = {
+    "cvs_qualify_f16_dev": (C.c_int, [_F16, _F16, _F16, P(qualifier_params), _vp]),
+    "cvs_qualify_f32_dev": (C.c_int, [_F32, _F32, _F32, P(qualifier_params), _vp]),
+    "cvs_matte_mix_f16_dev": (C.c_int, [_F16, _F16, _F16, _F16, P(matte_mix_params), _vp]),
+    "cvs_matte_mix_f32_dev": (C.c_int, [_F32, _F32, _F32, _F32, P(matte_mix_params), _vp]),
+}
+
 # the same for include/canvas_perspective.h (corner pin)
 PERSPECTIVE_SIGNATURES = {
     "cvs_perspective_f32_dev": (C.c_int, [_F32, _F32, P(perspective_params), _vp]),
@@ -427,7 +470,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or make -C canvas_amd/csrc).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()) + list(YCC420_SIGNATURES.items()) + list(PRIMARY_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCOPE_SIGNATURES.items()) + list(LUT3D_SIGNATURES.items()) + list(PERSPECTIVE_SIGNATURES.items()) + list(DEINTERLACE_SIGNATURES.items()) + list(MEDIAN_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + list(YCC422_SIGNATURES.items()) + list(YCC420_SIGNATURES.items()) + list(PRIMARY_SIGNATURES.items()) + list(SECONDARY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib

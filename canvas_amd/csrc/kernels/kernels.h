@@ -493,6 +493,27 @@ typedef struct {
 } cvk_temporal_params;
 int cvk_temporal_denoise(const cvk_temporal_params *tp, int neighbours, int cus, void *stream);
 
+/* Secondaries (secondary_ops.hip, DESIGN.md "Secondaries"): the HSL qualifier and the mix through a matte.  `w` (the window
+ * written) inside every view; the views are of one format (half: rgba_f16, else rgba_f32) and any of them may be the same
+ * buffer.  What host/secondary.c worked out of a cvs_qualifier: the hue centre, half width and outer edge in sextants, and per
+ * value range the two outer edges; the reciprocals are read only where their softness is > 0 (the *_soft members).  An axis
+ * whose member (hue, sat, luma) is 0 contributes exactly 1.  One arithmetic flavour: every operation is rounded on its own in
+ * both (the unit is not rebuilt with -DCVS_CONTRACT). */
+typedef struct {
+    float low, high, lo_edge, hi_edge, inv_lo, inv_hi;
+    int soft_lo, soft_hi;      /* soft_low > 0, soft_high > 0 */
+} cvk_value_range;
+typedef struct {
+    float hc, hw, h_edge, inv_hs;
+    int hue_soft;              /* softness > 0 */
+    cvk_value_range sat, luma;
+    int hue, saturation, lum;  /* which axes qualify */
+    int invert, matte;         /* m = 1 - m; (a', a', a', 1) instead of the qualified pixel */
+} cvk_qualify_params;
+/* key: the frame that is measured, or NULL: the source is qualified against itself */
+int cvk_qualify(const cvk_qualify_params *qp, cvk_view out, cvk_view src, const cvk_view *key, cvk_rect w, int half, int cus, void *stream);
+int cvk_matte_mix(cvk_view out, cvk_view a, cvk_view b, cvk_view matte, cvk_rect w, int luma, int invert, int half, int cus, void *stream);
+
 /* the contracted twins, as the host sees them (same signatures; built from the same sources with -DCVS_CONTRACT) */
 #ifndef CVS_CONTRACT
 int cvk_gain_offset_f16_fma(cvk_view out, cvk_view in, cvk_rect r, float gain, float offset, void *stream);

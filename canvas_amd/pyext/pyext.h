@@ -159,6 +159,7 @@ int init_transform(PyObject *module);
 int init_scope(PyObject *module);
 int init_lut3d(PyObject *module);
 int init_primary(PyObject *module);
+int init_secondary(PyObject *module);
 int init_perspective(PyObject *module);
 int init_workspace(PyObject *module);
 int init_ycc422(PyObject *module);

@@ -415,7 +415,7 @@ PyMODINIT_FUNC PyInit_process(void) {
     if (import_basetypes() != 0) { Py_DECREF(m); return NULL; }
     init_half();
     if (pyext_add_type(m, "VideoSource", &py_type_VideoSource) < 0 || init_framefuncs(m) < 0 || init_animation(m) < 0 || init_frames(m) < 0 ||
-        init_sources(m) < 0 || init_fields(m) < 0 || init_deint(m) < 0 || init_blur(m) < 0 || init_key(m) < 0 || init_matte(m) < 0 || init_median(m) < 0 || init_temporal(m) < 0 || init_transform(m) < 0 || init_scope(m) < 0 || init_lut3d(m) < 0 || init_primary(m) < 0 || init_perspective(m) < 0 || init_workspace(m) < 0 || init_dv(m) < 0 || init_ycc422(m) < 0 || init_ycc420(m) < 0) {
+        init_sources(m) < 0 || init_fields(m) < 0 || init_deint(m) < 0 || init_blur(m) < 0 || init_key(m) < 0 || init_matte(m) < 0 || init_median(m) < 0 || init_temporal(m) < 0 || init_transform(m) < 0 || init_scope(m) < 0 || init_lut3d(m) < 0 || init_primary(m) < 0 || init_secondary(m) < 0 || init_perspective(m) < 0 || init_workspace(m) < 0 || init_dv(m) < 0 || init_ycc422(m) < 0 || init_ycc420(m) < 0) {
         Py_DECREF(m);
         return NULL;
     }

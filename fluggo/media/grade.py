@@ -275,3 +275,20 @@ def write_cube_1d(table, domain_min=(0.0, 0.0, 0.0), domain_max=(1.0, 1.0, 1.0),
     for row in rows:
         lines.append("%r %r %r" % tuple(row))
     return "\n".join(lines) + "\n"
+
+
+def secondary(source, graded, hue=None, saturation=None, luma=None, invert=False, choke=0, feather=None):
+    """A secondary grade as a graph of `fluggo.media.process` nodes: `graded` where the pixels of `source` fall inside the hue,
+    saturation and luma ranges, `source` elsewhere.
+
+        qualified = VideoQualifierFilter(source, hue, saturation, luma, invert=invert)     # source's alpha times the matte
+        matte     = VideoMatteFilter(qualified, choke, feather)                              # left out when choke == 0 and feather is None
+        out       = VideoMatteMixFilter(source, graded, matte)
+
+    hue is (center, width, softness) in degrees, saturation and luma are (low, high, soft_low, soft_high); None: the axis does not
+    qualify.  Returns the last node."""
+    from fluggo.media import process
+    matte = process.VideoQualifierFilter(source, hue=hue, saturation=saturation, luma=luma, invert=invert)
+    if choke != 0 or feather is not None:
+        matte = process.VideoMatteFilter(matte, choke=choke, feather=feather)
+    return process.VideoMatteMixFilter(source, graded, matte)
