@@ -11,14 +11,37 @@ GROUPS lists every group with the extents it runs at; tests/test_extents_cpu.py 
 expectations on the reference side (tests/reference_library.py), tests/test_extents_gpu.py runs it in a guarded arena.
 
 Not in this catalogue: the DV pair (cvs_reconstruct_dv_dev, cvs_subsample_dv_dev) -- the DV raster is fixed at 720 x 480, so
-those two entries have no extent to vary -- and the five flat-array entries, which have no window."""
+those two entries have no extent to vary -- and the five flat-array entries, which have no window.
+
+The entries of the extension headers are here too, on the operands of their own catalogues (tests/deinterlace_cases.py,
+temporal_cases.py, perspective_cases.py, ycc422_cases.py, ycc420_cases.py; thin groups over median_cases.py, primary_cases.py and
+secondary_cases.py), at the lines of their launchers: rowstream::shape with `made` lanes for the row-stream pair, warp::launch_bands
+for the corner pin, cvs::plan_strips and table_grid for the edges.
+
+One line stays without a case: plan_strips refuses a launch of more than 2^31 - 2^20 units (runs per row times rows of units),
+the margin its kernels' `int u += stride` walk needs.  With coordinates within 2^30 that takes a raster of hundreds of
+gigapixels -- at the 126 columns of a run and one row of units per row, 2^31 units are 270 gigapixels, some two terabytes of
+half pixels -- which no buffer a test can hold reaches.  The refusal is read, not run."""
 import ctypes as C
+import functools
 
 import numpy as np
 
 from canvas_amd import _lib
-from canvas_amd.abi import box2i
+from canvas_amd.abi import HostFrame, box2i
+from tests import deinterlace_cases as dc
+from tests import deinterlace_model as dm
 from tests import entry_cases as ec
+from tests import median_cases as mdc
+from tests import median_model as mdm
+from tests import primary_cases as prc
+from tests import secondary_cases as sec
+from tests import temporal_cases as tc
+from tests import temporal_model as tpm
+from tests import ycc420_cases as y420
+from tests import ycc420_model as y420m
+from tests import ycc422_cases as y422
+from tests import ycc422_model as y422m
 from tests.entry_cases import blank, px, px16, px32
 from tests.util import f32p
 
@@ -517,6 +540,233 @@ def workspace_stack(cvs, width, height):
     return cases
 
 
+# ------------------------------------------------------------------ the extension headers: the row-stream pair
+
+def _held(codes, full, cur):
+    return HostFrame(full, np.uint16, codes, cur)
+
+
+@functools.lru_cache(maxsize=1)
+def _thirds(full):
+    """(a case is run several times on the same pictures -- the reference side, both poisons -- and four million rows take a second to draw)"""
+    return _read_only(dm.thirds(np.random.default_rng(4100), full, dc.THRESHOLD, dc.SOFTNESS))
+
+
+@functools.lru_cache(maxsize=1)
+def _sequence(full):
+    return _read_only(tpm.sequence(np.random.default_rng(4200), full, tc.THRESHOLD, tc.SOFTNESS))
+
+
+def _read_only(arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return tuple(arrays)
+
+
+def deinterlace_adaptive(cvs, width, height):
+    """tests/deinterlace_model.py's thirds (at one or two columns: the third whose neighbours straddle the ramp), so that with the
+    catalogue's nonzero softness the blend runs beside both copies.  Per window field 0 between two neighbours and field 1 with
+    the previous frame alone (a clip's last frame); on the whole buffer also field 1 between two."""
+    cases = []
+    for wname, full, cur in windows(width, height):
+        for field, which in [(0, "both"), (1, "prev")] + ([(1, "both")] if wname == "whole" else []):
+            def case(fac, full=full, cur=cur, field=field, which=which):
+                prev, now, nxt = (_held(codes, full, cur) for codes in _thirds(full))
+                a = fac.frame(prev)
+                b = fac.frame(now)
+                c = fac.frame(nxt) if which == "both" else None
+                out = fac.frame(blank(True, full), out=True, cmp="f16")
+                p = _lib.deinterlace_adaptive(field, dc.THRESHOLD, dc.SOFTNESS)
+                return cvs.cvs_deinterlace_adaptive_f16_dev(out.ref(), a.ref(), b.ref(), c.ref() if c else None, C.byref(p), fac.stream)
+            cases.append((_name("adaptive deinterlace, field %d, neighbours %s" % (field, which), width, height, wname), case))
+    return cases
+
+
+def temporal(cvs, width, height, radius):
+    """tests/temporal_model.py's sequence; radius 1: the two near neighbours, radius 2: all four, every channel, on the ramp."""
+    which = tc.WHICH["near" if radius == 1 else "all"]
+    cases = []
+    for wname, full, cur in windows(width, height):
+        def case(fac, full=full, cur=cur):
+            prev2, prev1, now, next1, next2 = (_held(codes, full, cur) for codes in _sequence(full))
+            frames = [fac.frame(f) if on else None for f, on in zip((prev2, prev1), which[:2])]
+            frames.append(fac.frame(now))
+            frames += [fac.frame(f) if on else None for f, on in zip((next1, next2), which[2:])]
+            out = fac.frame(blank(True, full), out=True, cmp="f16")
+            p = _lib.temporal_denoise(tc.THRESHOLD, tc.SOFTNESS, tpm.ALL)
+            refs = [f.ref() if f else None for f in frames]
+            return cvs.cvs_temporal_denoise_f16_dev(out.ref(), refs[0], refs[1], refs[2], refs[3], refs[4], C.byref(p), fac.stream)
+        cases.append((_name("temporal denoise, radius %d" % radius, width, height, wname), case))
+    return cases
+
+
+# ------------------------------------------------------------------ the corner pin
+
+PIN_REACH = 20000           # rows between the map's origin and its vanishing line, where the target has them
+
+
+def pin_map(width, height, near):
+    """(h, target origin, source origin, source buffer) of a true perspective for a target of width x height (h6, h7 != 0: a
+    parallelogram would give the affine kernel's bytes).  With x, y counted from the target origin and D = the reach,
+
+        w = 1 + x / (8 * source width) - y / D
+
+    so the vanishing line w = 0 lies D rows below the origin, which is placed so that the line crosses a tall target 20 rows above
+    its last row (of 524 320 rows: inside the launcher's second band, which starts at row 524 280); a target of a few rows has the
+    line four rows below it.  One map cannot vary from row to row both far from its line and next to it (v is a Moebius function
+    of y: its slope falls with 1 / w^2), so there are two:
+
+        far    u = (x + y / 1024 + 1/4) / w;  v = (2 - 0.4 y) / w.  Above the origin v climbs towards 0.4 D, the source's height,
+               and differs from row to row for some 400 000 rows: a row of the first band put in another's place shows.  The D rows
+               between the origin and the line fall outside the source, the rows beyond the line have w <= 0: both zero.
+        near   u = 1/4 + x / w;  v = 4 + c / w with c D = the source's height less 8: k rows above the line the middle column
+               samples source row 4 + c D / k -- 404, 425, ... 4004, 8004 in the second band's first 20 rows -- and the rows
+               beyond it are zero: the second band holds drawn and undrawn rows, every drawn one different.
+
+    The source is as wide as the target and 64 columns more, so u runs off it on both sides of a wide target."""
+    reach = max(8, min(PIN_REACH, height // 2))
+    line = height - 20 if height >= 64 else height + 4
+    sw, sh = width + 64, int(0.4 * reach) + 8
+    h6, h7 = 1.0 / (8.0 * sw), -1.0 / reach
+    if near:
+        u0, v0, c = 0.25, 4.0, (sh - 8.0) / reach
+        h = (1.0 + u0 * h6, u0 * h7, u0, v0 * h6, v0 * h7, v0 + c, h6, h7, 1.0)
+    else:
+        h = (1.0, 1.0 / 1024.0, 0.25, 0.0, -0.4, 2.0, h6, h7, 1.0)
+    return h, (width // 2, line - reach), (sw // 2, 0), (0, 0, sw - 1, sh - 1)
+
+
+def perspective(cvs, width, height, half):
+    """width x height is the TARGET.  A bilinear and a nearest case of each of pin_map's two maps; the origins go through fac.box,
+    as tests/perspective_cases.py params() takes them."""
+    tfull = (0, 0, width - 1, height - 1)
+    cases = []
+    for near in (False, True):
+        h, to, so, sfull = pin_map(width, height, near)
+        for filt in (_lib.TRANSFORM_BILINEAR, _lib.TRANSFORM_NEAREST):
+            def case(fac, h=h, to=to, so=so, sfull=sfull, filt=filt):
+                t, s = fac.box(to[0], to[1], to[0], to[1]), fac.box(so[0], so[1], so[0], so[1])
+                p = _lib.perspective(h, (t.min.x, t.min.y), (s.min.x, s.min.y), filt)
+                src = fac.frame(px(np.random.default_rng(4300), half, sfull))
+                out = fac.frame(blank(half, tfull), out=True, cmp="f16" if half else "f32")
+                entry = cvs.cvs_perspective_f16_dev if half else cvs.cvs_perspective_f32_dev
+                return entry(out.ref(), src.ref(), C.byref(p), fac.stream)
+            cases.append((_name("perspective %s, %s map, %s" % ("f16" if half else "f32", "near" if near else "far", "bilinear" if filt else "nearest"),
+                                width, height, "whole"), case))
+    return cases
+
+
+# ------------------------------------------------------------------ the 4:2:2 and 4:2:0 edges
+
+# width x height of the RASTER; the frame is the raster's window or the inset one.  Where the 128 KiB transfer table lives is
+# table_placement.hpp's: gathered through L2 up to kGatherUpTo pixels, staged into LDS above.  Every raster here but the last of
+# each list lies below that line and runs the gathered form; the last, of two columns, is the first two-column row in the LDS form
+# (tests/test_extents_cpu.py test_the_tallest_raster_alone_is_above_the_table_line reads the constant and holds the lists to this).
+YCC422_RASTERS = [(2, 65535), (2, 65536), (4, 70001), (70002, 3), (131074, 2), (2, 4194305)]      # any height is legal
+YCC420_RASTERS = [(2, 65534), (2, 65536), (4, 70002), (70002, 4), (131074, 2), (2, 4194306)]      # even heights
+YCC_FEW = [(2, 65536), (131074, 2)]
+
+
+def ycc422(cvs, width, height, layout):
+    """Both directions; the raster's own window with the least strides, and the inset window with padded ones."""
+    strides, lines = y422m.least(layout, width, height)
+    cases = []
+    for n, (wname, full, cur) in enumerate(windows(width, height)):
+        frame = full if wname == "whole" else cur
+        padded = [s + p for s, p in zip(strides, y422.PADS[layout][n])]
+        for direction in ("reconstruct", "subsample"):
+            spec = dict(direction=direction, layout=layout, matrix="601" if n else "709", width=width, height=height, strides=padded, lines=lines,
+                        full=frame, seed=4400 + n)
+            cases.append((_name(y422.name(spec), width, height, wname), y422.make_case(cvs, spec)))
+    return cases
+
+
+def ycc420(cvs, width, height, layout):
+    """Both directions.  Below 2^19 rows: the raster's window at left siting, the inset window with padded strides at centre siting
+    (the import keeps a lane for the column on the left: runs of 62 columns) and full range, the raster's window at top-left siting
+    without a transfer table.  At the tallest raster, where the table is in LDS: centre siting with the table, top-left without."""
+    strides, lines = y420m.least(layout, width, height)
+    wins = windows(width, height)
+    whole, inset = wins[0][1], wins[-1][2]
+    if len(wins) == 1:
+        forms = [("whole", whole, 0, "center", "studio", "709", "709"), ("whole", whole, 0, "topleft", "studio", "2020", "none")]
+    else:
+        forms = [("whole", whole, 0, "left", "studio", "709", "709"), ("inset", inset, 1, "center", "full", "601", "709"),
+                 ("whole", whole, 0, "topleft", "studio", "2020", "none")]
+    cases = []
+    for n, (wname, frame, pad, siting, range_, matrix, transfer) in enumerate(forms):
+        padded = [s + p for s, p in zip(strides, y420.PADS[layout][pad])]
+        for direction in ("reconstruct", "subsample"):
+            spec = dict(direction=direction, layout=layout, siting=siting, range=range_, matrix=matrix, transfer=transfer, width=width, height=height,
+                        strides=padded, lines=lines, full=frame, seed=4500 + n)
+            cases.append((_name(y420.name(spec), width, height, wname), y420.make_case(cvs, spec)))
+    return cases
+
+
+# ------------------------------------------------------------------ the median, the primary, the secondaries
+
+# Thin groups over the operands of tests/median_cases.py, primary_cases.py and secondary_cases.py: what puts the entries under the
+# headers' completeness check at 65 536 rows and 70 001 columns.  Their widest and tallest windows (131 073 columns, 4 194 305
+# rows) stay where they are, in the extent tests of their harness modules.
+THIN = [(2, 65536), (70001, 3)]
+
+
+def median(cvs, width, height):
+    cases = []
+    for wname, full, cur in windows(width, height):
+        for half, radius, threshold, channels in ((True, 2, mdm.THRESHOLD, "rgba"), (False, 1, 0.0, "ga")):
+            def case(fac, full=full, cur=cur, half=half, radius=radius, threshold=threshold, channels=channels):
+                src = fac.frame(mdc.source(np.random.default_rng(4600), half, full, cur))
+                out = fac.frame(blank(half, full), out=True, cmp="f16" if half else "f32")
+                p = _lib.median(radius, threshold, mdm.mask_of(channels))
+                entry = cvs.cvs_median_f16_dev if half else cvs.cvs_median_f32_dev
+                return entry(out.ref(), src.ref(), C.byref(p), fac.stream)
+            cases.append((_name("median %s, radius %d" % ("f16" if half else "f32", radius), width, height, wname), case))
+    return cases
+
+
+def primary(cvs, width, height):
+    """Out of place in both formats (curves, matrix, curves; curves alone twice), and the half frame in place."""
+    cases = []
+    for wname, full, cur in windows(width, height):
+        for half, stages, in_place in ((True, prc.STAGES[0], False), (False, prc.STAGES[6], False), (True, prc.STAGES[4], True)):
+            def case(fac, full=full, cur=cur, half=half, stages=stages, in_place=in_place):
+                cmp = "f16" if half else "f32"
+                src = fac.frame(px(np.random.default_rng(4700), half, full, cur), out=in_place, cmp=cmp, in_place=in_place)
+                out = src if in_place else fac.frame(blank(half, full), out=True, cmp=cmp)
+                pre, post = prc._tables(fac, stages)
+                p = prc._params(stages)
+                return prc._entry(cvs, half)(out.ref(), src.ref(), C.byref(p), pre, post, fac.stream)
+            cases.append((_name("primary %s%s" % ("f16" if half else "f32", ", in place" if in_place else ""), width, height, wname), case))
+    return cases
+
+
+def secondaries(cvs, width, height):
+    """The qualifier on all three axes with a key frame of its own, and the mix through a matte's luma, in both formats; every
+    input's current window narrowed its own way (tests/secondary_cases.py _narrowed)."""
+    cases = []
+    for wname, full, cur in windows(width, height):
+        for half in (True, False):
+            cmp, fmt = ("f16", "f16") if half else ("f32", "f32")
+
+            def qualify(fac, full=full, cur=cur, half=half, cmp=cmp):
+                rng = np.random.default_rng(4800)
+                src = fac.frame(sec.picture(rng, half, full, cur))
+                key = fac.frame(sec.picture(rng, half, full, sec._narrowed(cur, 1)))
+                out = fac.frame(blank(half, full), out=True, cmp=cmp)
+                p = sec.params(sec.QUALIFIERS[7])
+                return sec._qualify(cvs, half)(out.ref(), src.ref(), key.ref(), C.byref(p), fac.stream)
+
+            def mix(fac, full=full, cur=cur, half=half, cmp=cmp):
+                rng = np.random.default_rng(4850)
+                ins = [fac.frame(sec.picture(rng, half, full, w)) for w in (cur, sec._narrowed(cur, 1), sec._narrowed(cur, 2))]
+                out = fac.frame(blank(half, full), out=True, cmp=cmp)
+                p = _lib.matte_mix(True, False)
+                return sec._mix(cvs, half)(out.ref(), ins[0].ref(), ins[1].ref(), ins[2].ref(), C.byref(p), fac.stream)
+            cases += [(_name("qualify %s" % fmt, width, height, wname), qualify), (_name("matte mix %s" % fmt, width, height, wname), mix)]
+    return cases
+
+
 # ------------------------------------------------------------------ every group at every extent
 
 def _groups():
@@ -557,6 +807,20 @@ def _groups():
           ("lut3d[f16-33]", auto, lambda cvs, w, h: lut3d(cvs, w, h, True, 33), both + STREAM_ROWS, 0), ("lut3d[f32-33]", auto, lambda cvs, w, h: lut3d(cvs, w, h, False, 33), both, 0)]
     g += [("scope_counts[%d]" % kind, auto, lambda cvs, w, h, kind=kind: scope_counts(cvs, w, h, kind), both, None) for kind in (_lib.SCOPE_HISTOGRAM, _lib.SCOPE_WAVEFORM)]
     g += [("scope_render", auto, scope_render, both, None)]
+    # the extension headers.  Halos, read from the models: a made row of the deinterlacer takes the rows above and below it, and
+    # its weight -- like the denoise's -- the 3 x 3 differences around the pixel (deinterlace_model.neighbourhood): 1 row.  The
+    # 4:2:0 import reads chroma rows c - 1 and c + 1 for luma rows 2c and 2c + 1 (ycc420_model.vertical), the export luma row
+    # 2c - 1 (filter_chroma): 2 rows.  The 4:2:2 edges work along a row: 0.  The corner pin reads the source wherever h says.
+    g += [("deinterlace_adaptive", auto, deinterlace_adaptive, both + STREAM_ROWS, 1),
+          ("temporal[1]", auto, lambda cvs, w, h: temporal(cvs, w, h, 1), both, 1),
+          ("temporal[2]", auto, lambda cvs, w, h: temporal(cvs, w, h, 2), both + STREAM_ROWS, 1)]
+    g += [("perspective[%s]" % ("f16" if half else "f32"), auto, lambda cvs, w, h, half=half: perspective(cvs, w, h, half), both + (TRANSFORM_ROWS if half else TRANSFORM_ROWS[-1:]), None)
+          for half in (True, False)]
+    g += [("ycc422[%s]" % layout, auto, lambda cvs, w, h, layout=layout: ycc422(cvs, w, h, layout), YCC422_RASTERS if layout in ("v210", "planar8") else YCC_FEW, 0)
+          for layout in y422.LAYOUT_NAMES]
+    g += [("ycc420[%s]" % layout, auto, lambda cvs, w, h, layout=layout: ycc420(cvs, w, h, layout), YCC420_RASTERS if layout in ("nv12", "planar10") else YCC_FEW, 2)
+          for layout in y420.LAYOUT_NAMES]
+    g += [("median", auto, median, THIN, 2), ("primary", auto, primary, THIN, 0), ("secondaries", auto, secondaries, THIN, 0)]
     return g
 
 

@@ -9,6 +9,9 @@ CPU oracle -- the reference's pixel code in `int` -- or to the numpy models, on 
   MODELLED   entries the reference has no C for, tied to the numpy models their own GPU modules use (fields_model, key_model,
              matte_model, transform_model, unsharp_model, lut3d_model, scope_model over the oracle's display bytes, mpeg2_model,
              mpeg2_reconstruct_model)
+  EXTENSIONS the entries of the extension headers, which the reference has no code for either: the adaptive deinterlacer, the
+             temporal denoise, the corner pin, the 4:2:2 and 4:2:0 edges, the median, the primary and the secondaries, each
+             through the model of its own GPU module
   and the workspace's device slot, which ReferenceLibrary answers with orc_workspace_get_frame_f32
 
 tests/test_far_windows_cpu.py and tests/test_far_windows_gpu.py run the catalogue of tests/entry_cases.py through it far from
@@ -437,6 +440,159 @@ def _subsample_mpeg2(image, frame, width, height):
         plane[:w.shape[0], :w.shape[1]] = w
 
 
+# ---- the extension headers' entries: no reference code, only the numpy models of their own GPU modules.  Every one of these
+# models works on whole arrays (none walks the rows in Python, as fields_model.field_to_frame does), so it is the model itself,
+# not a restatement, that tests/test_extents_cpu.py runs at four million rows.
+
+def _frame_or_none(ref, dtype=np.uint16):
+    """A frame argument as the models take one: (pixels over the full window, full window, current window or None); None for NULL"""
+    if ref is None:
+        return None
+    c = _struct(ref)
+    return (_pixels_of(c, dtype), c.full_window.tuple(), _tuple_or_none(c.current_window))
+
+
+def _deinterlace(out, prev, cur, nxt, params):
+    from tests import deinterlace_model as dm
+    o, p = _struct(out), _struct(params)
+    after, win, _exact, _k = dm.expected(_pixels_of(o, np.uint16), o.full_window.tuple(), _frame_or_none(cur), _frame_or_none(prev), _frame_or_none(nxt),
+                                         p.field, p.threshold, p.softness, oracle.float_to_half)
+    _pixels_of(o, np.uint16)[...] = after
+    _set_window(o, win)
+
+
+def _temporal(out, prev2, prev1, cur, next1, next2, params):
+    from tests import temporal_model as tpm
+    o, p = _struct(out), _struct(params)
+    neighbours = [_frame_or_none(f) for f in (prev1, next1, prev2, next2)]           # the contract's order of summation
+    after, win, _exact, _w = tpm.expected(_pixels_of(o, np.uint16), o.full_window.tuple(), _frame_or_none(cur), neighbours, p.threshold, p.softness,
+                                          p.channels, oracle.float_to_half)
+    _pixels_of(o, np.uint16)[...] = after
+    _set_window(o, win)
+
+
+def _perspective(before, tfull, src, sfull, scur, params):
+    from tests import perspective_model as pm
+    p = _struct(params)
+    return pm.expected(before, tfull, src, sfull, scur, (tuple(p.h), tuple(p.target_origin), tuple(p.source_origin)), p.filter)
+
+
+def _median(before, tfull, src, sfull, scur, params):
+    """(the model works on bit patterns: an f32 frame as uint32)"""
+    from tests import median_model as mdm
+    p = _struct(params)
+    bits = (lambda a: a) if before.dtype == np.uint16 else (lambda a: a.view(np.uint32))
+    after, win = mdm.expected(bits(before), tfull, bits(src), sfull, scur, p.radius, p.threshold, p.channels)
+    return after.view(before.dtype), win
+
+
+def _primary(out, src, params, pre, post):
+    """In place too: the source is read before the target is written."""
+    from tests import primary_model as prm
+    o, s, p = _struct(out), _struct(src), _struct(params)
+    dtype = np.uint16 if isinstance(o, _lib.rgba_frame_f16_t) else np.float32
+
+    def curves(stage, address):
+        if stage.size == 0:
+            return None
+        table = _bytes_at(address, 3 * stage.size, np.float32).reshape(3, stage.size).T          # (planar: K of R, K of G, K of B)
+        return prm.Curves(table.copy(), (tuple(stage.domain_min), tuple(stage.domain_max)))
+    matrix = list(p.matrix) if p.flags & _lib.PRIMARY_MATRIX else None
+    after, win = prm.expected(_pixels_of(o, dtype).copy(), o.full_window.tuple(), _pixels_of(s, dtype).copy(), s.full_window.tuple(),
+                              _tuple_or_none(s.current_window), curves(p.pre, pre), matrix, curves(p.post, post))
+    _pixels_of(o, dtype)[...] = after
+    _set_window(o, win)
+
+
+def _qualify(out, src, key, params):
+    from tests import secondary_model as scm
+    o, p = _struct(out), _struct(params)
+    dtype = np.uint16 if isinstance(o, _lib.rgba_frame_f16_t) else np.float32
+    f = p.flags
+    q = scm.Qualifier(hue=(p.hue.center, p.hue.width, p.hue.softness) if f & _lib.QUAL_HUE else None,
+                      saturation=(p.saturation.low, p.saturation.high, p.saturation.soft_low, p.saturation.soft_high) if f & _lib.QUAL_SATURATION else None,
+                      luma=(p.luma.low, p.luma.high, p.luma.soft_low, p.luma.soft_high) if f & _lib.QUAL_LUMA else None,
+                      invert=bool(f & _lib.QUAL_INVERT), show_matte=bool(f & _lib.QUAL_SHOW_MATTE))
+    s, k = _frame_or_none(src, dtype), _frame_or_none(key, dtype)
+    args = (s[0].copy(), s[1], s[2], q) + ((k[0].copy(), k[1], k[2]) if k is not None else ())
+    after, win = scm.expected_qualify(_pixels_of(o, dtype).copy(), o.full_window.tuple(), *args)
+    _pixels_of(o, dtype)[...] = after
+    _set_window(o, win)
+
+
+def _matte_mix(out, a, b, matte, params):
+    from tests import secondary_model as scm
+    o, p = _struct(out), _struct(params)
+    dtype = np.uint16 if isinstance(o, _lib.rgba_frame_f16_t) else np.float32
+    args = [v for f in (a, b, matte) for v in _frame_or_none(f, dtype)]
+    args[0::3] = [pixels.copy() for pixels in args[0::3]]
+    after, win = scm.expected_mix(_pixels_of(o, dtype).copy(), o.full_window.tuple(), *args, luma=bool(p.flags & _lib.MMIX_LUMA), invert=bool(p.flags & _lib.MMIX_INVERT))
+    _pixels_of(o, dtype)[...] = after
+    _set_window(o, win)
+
+
+def _coded(image, nplanes):
+    img = _struct(image)
+    return [_bytes_at(img.data[k], img.stride[k] * img.line_count[k]).reshape(img.line_count[k], img.stride[k]) for k in range(nplanes)]
+
+
+def _name_of(table, value):
+    return next(name for name, v in table.items() if v == value)
+
+
+def _reconstruct_422(frame, image, width, height, layout, flags):
+    from tests import ycc422_model as y2
+    f, name = _struct(frame), _name_of(y2.LAYOUTS, layout)
+    raster = y2.reconstruct_model(name, _coded(image, y2.PLANES[name]), width, height, _gcc_table(0), oracle.float_to_half, "709" if flags & _lib.YCC_REC709 else "601")
+    after, win = y2.expected_frame(_pixels_of(f, np.uint16), f.full_window.tuple(), raster, width, height)
+    _pixels_of(f, np.uint16)[...] = after
+    _set_window(f, win)
+
+
+def _subsample_422(image, frame, width, height, layout, flags):
+    """The planes the call writes: the least stride's bytes of the raster's lines; everything else keeps what it held."""
+    from tests import ycc422_model as y2
+    f, name = _struct(frame), _name_of(y2.LAYOUTS, layout)
+    want = y2.subsample_model(name, _pixels_of(f, np.uint16), f.full_window.tuple(), f.current_window.tuple(), width, height, _gcc_table(2),
+                              "709" if flags & _lib.YCC_REC709 else "601")
+    for plane, w in zip(_coded(image, y2.PLANES[name]), want):
+        plane[:w.shape[0], :w.shape[1]] = w
+
+
+def _flags_420(flags):
+    from tests import ycc420_model as y0
+    pick = lambda table, mask: _name_of(table, flags & mask)
+    return (pick(y0.MATRIX_FLAGS, 2 | 4), pick(y0.RANGE_FLAGS, 8), pick(y0.SITING_FLAGS, 16 | 32), pick(y0.TRANSFER_FLAGS, 64))
+
+
+def _reconstruct_420(frame, image, width, height, layout, flags):
+    from tests import ycc420_model as y0
+    f, name = _struct(frame), _name_of(y0.LAYOUTS, layout)
+    matrix, range_, siting, transfer = _flags_420(flags)
+    raster = y0.reconstruct_model(name, _coded(image, y0.PLANES[name]), width, height, _gcc_table(0), oracle.float_to_half, matrix, range_, siting, transfer)
+    after, win = y0.expected_frame(_pixels_of(f, np.uint16), f.full_window.tuple(), raster, width, height)
+    _pixels_of(f, np.uint16)[...] = after
+    _set_window(f, win)
+
+
+def _subsample_420(image, frame, width, height, layout, flags):
+    from tests import ycc420_model as y0
+    f, name = _struct(frame), _name_of(y0.LAYOUTS, layout)
+    matrix, range_, siting, transfer = _flags_420(flags)
+    want = y0.subsample_model(name, _pixels_of(f, np.uint16), f.full_window.tuple(), f.current_window.tuple(), width, height, _gcc_table(2),
+                              matrix, range_, siting, transfer)
+    for plane, w in zip(_coded(image, y0.PLANES[name]), want):
+        plane[:w.shape[0], :w.shape[1]] = w
+
+
+EXTENSIONS = {"cvs_deinterlace_adaptive_f16_dev": _deinterlace, "cvs_temporal_denoise_f16_dev": _temporal,
+              "cvs_perspective_f16_dev": _model_call(_perspective), "cvs_perspective_f32_dev": _model_call(_perspective),
+              "cvs_reconstruct_422_dev": _reconstruct_422, "cvs_subsample_422_dev": _subsample_422,
+              "cvs_reconstruct_420_dev": _reconstruct_420, "cvs_subsample_420_dev": _subsample_420,
+              "cvs_median_f16_dev": _model_call(_median), "cvs_median_f32_dev": _model_call(_median),
+              "cvs_primary_f16_dev": _primary, "cvs_primary_f32_dev": _primary,
+              "cvs_qualify_f16_dev": _qualify, "cvs_qualify_f32_dev": _qualify, "cvs_matte_mix_f16_dev": _matte_mix, "cvs_matte_mix_f32_dev": _matte_mix}
+
 MODELLED = {"cvs_blur_over_f16_batch_dev": _blur_over_batch, "cvs_frame_to_bytes_dev": _to_bytes, "cvs_frame_to_rgba8_intent_dev": _to_rgba8_intent,
             "cvs_lut3d_f16_dev": _lut3d, "cvs_lut3d_f32_dev": _lut3d, "cvs_scope_counts_f16_dev": _scope_counts,
             "cvs_scope_render_f16_dev": _scope_render, "cvs_reconstruct_mpeg2_dev": _reconstruct_mpeg2, "cvs_subsample_mpeg2_dev": _subsample_mpeg2,
@@ -472,7 +628,7 @@ class ReferenceLibrary(OracleAsLibrary):
     """OracleAsLibrary with the wider map: what tests/extent_cases.py is held to.  The workspace's device slot is the oracle's
     stack (orc_workspace_get_frame_f32, as tests/test_gpu_parity.py test_workspace_stack_host_and_device holds it) over
     sources whose host slots pull through the case's own device slot, which on this side works on host memory."""
-    tables = (ORACLE, dict(COMPOSED, **MODELLED))
+    tables = (ORACLE, dict(COMPOSED, **MODELLED, **EXTENSIONS))
 
     def workspace_create(self):
         return []

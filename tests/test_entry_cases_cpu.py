@@ -21,14 +21,26 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 NOT_RECORDED = {}
 
 
-def device_entries():
-    """Every cvs_*_dev function the header declares whose last parameter is a cvs_stream_t."""
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+def header_files():
+    """Every header of the library, canvas_hip.h and the extension headers beside it: found, not listed."""
+    import glob
+    return sorted(glob.glob(os.path.join(os.path.dirname(HEADER), "canvas*.h")))
+
+
+def declared(text):
+    """[(entry, parameter text)] of every `CVS_EXPORT int cvs_*_dev(...);` a header's text declares outside its comments."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.findall(r"CVS_EXPORT\s+int\s+(cvs_\w+_dev)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
+
+
+def device_entries(texts=None):
+    """Every cvs_*_dev function whose last parameter is a cvs_stream_t: of include/canvas_hip.h, or of the header texts handed in."""
     found = {}
-    for name, params in re.findall(r"CVS_EXPORT\s+int\s+(cvs_\w+_dev)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        last = params.split(",")[-1].split()
-        if last[0] == "cvs_stream_t":
-            found[name] = last[-1]
+    for text in [open(HEADER).read()] if texts is None else texts:
+        for name, params in declared(text):
+            last = params.split(",")[-1].split()
+            if last[0] == "cvs_stream_t":
+                found[name] = last[-1]
     return found
 
 

@@ -16,7 +16,7 @@ from tests import entry_cases as ec
 from tests import extent_cases as xc
 from tests import fields_model as fm
 from tests import reference_library as rl
-from tests.test_entry_cases_cpu import HEADER, HostOnly, Recorder
+from tests.test_entry_cases_cpu import HEADER, HostOnly, Recorder, declared, header_files
 
 # (group prefix, (width, height)) -> the reference's file and line, where its own `int` code is undefined at that extent and
 # the extent is kept out for that group only.  At most one pair in ten, and no group may lose both 65 536 and 70 001 rows.
@@ -142,27 +142,45 @@ def test_the_undefined_table_is_within_its_cap():
         assert re.search(r"\.c:\d+", reason), reason
 
 
-def frame_taking_entries():
-    """Every cvs_*_dev function of the three headers that takes a frame and a stream."""
+def test_the_tallest_raster_alone_is_above_the_table_line():
+    """Which rasters of the edge groups run which table placement, from kernels/table_placement.hpp's own constant: every raster
+    but the tallest of each list is gathered through L2, the tallest -- two columns wide -- stages the table into LDS."""
     import os
+    text = open(os.path.join(os.path.dirname(os.path.dirname(HEADER)), "canvas_amd", "csrc", "kernels", "table_placement.hpp")).read()
+    shift = re.search(r"constexpr long long kGatherUpTo = 1LL << (\d+);", text)
+    assert shift and re.search(r"pixels <= kGatherUpTo \? kTableL2 : kTableLds", text)
+    line = 1 << int(shift.group(1))
+    for rasters in (xc.YCC422_RASTERS, xc.YCC420_RASTERS):
+        assert [w * h > line for w, h in rasters] == [False] * (len(rasters) - 1) + [True] and rasters[-1][0] == 2
+    assert all(w * h <= line for w, h in xc.YCC_FEW)
+
+
+def frame_taking_entries(texts=None):
+    """Every cvs_*_dev function of every header (include/canvas*.h, found by glob) that takes a frame and a stream."""
     found = set()
-    for name in ("canvas_hip.h", "canvas_scope.h", "canvas_lut3d.h"):
-        text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(os.path.dirname(HEADER), name)).read(), flags=re.S)
-        for entry, params in re.findall(r"CVS_EXPORT\s+int\s+(cvs_\w+_dev)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+    for text in texts if texts is not None else [open(name).read() for name in header_files()]:
+        for entry, params in declared(text):
             if "rgba_frame_f" in params or "cvs_chain_job" in params:
                 found.add(entry)
     return found
+
+
+# the edges' rasters have even widths: what reaches them at 70 001 columns and more is a raster of 70 002
+AT_EXTENT = {(2, 65536): [(2, 65536)], (70001, 3): [(70001, 3), (70002, 3), (70002, 4)]}
 
 
 def test_every_frame_taking_entry_is_reached_at_both_extents():
     """At 65 536 rows and at 70 001 columns, by a call the stand-in sees; the DV pair is the only exemption (no extent to vary)."""
     entries = frame_taking_entries()
     assert len(entries) >= 47 and "cvs_scope_counts_f16_dev" in entries and "cvs_lut3d_f16_dev" in entries and "cvs_half_lookup_dev" not in entries
+    assert len(header_files()) >= 11 and {"cvs_reconstruct_420_dev", "cvs_temporal_denoise_f16_dev", "cvs_qualify_f32_dev"} <= entries
     for extent in ((2, 65536), (70001, 3)):
         rec = Recorder()
         for gid, _pin, build, extents, _halo in xc.GROUPS:
-            if extent in extents:
-                for what, case in build(rec, *extent):
+            for at in AT_EXTENT[extent]:
+                if at not in extents:
+                    continue
+                for what, case in build(rec, *at):
                     assert case(HostOnly(rec, 1)) == 0
         reached = {n for n, _ in rec.calls if n.startswith("cvs_") and n.endswith("_dev")}
         assert reached <= entries, sorted(reached - entries)

@@ -7,7 +7,8 @@ Elsewhere in the suite the tallest window has 4320 rows and the widest 7680 colu
 poisons, at 65 535, 65 536 and 70 001 rows, at 70 001 and 131 073 columns, and at the row counts where a launcher's own
 arithmetic changes: a launcher that mis-forms a row index writes into a guard and is reported by name.  The expectation is the
 reference side's (tests/reference_library.py: the CPU oracle in the flavour of the run, or the numpy models), never another run
-of the library; tests/test_extents_cpu.py proves it without a GPU.
+of the library; tests/test_extents_cpu.py proves it without a GPU.  The entries of the extension headers run at the lines of their
+own launchers: the row-stream pair and the edges up to four million rows, the corner pin into the second band of its launcher.
 
 Per case: return code 0, cvs_last_error() empty, every reported window the reference's, every output the reference's (code for
 code, or canonical codes where the object's cmp says so; inside the reported window alone for extent_cases.WINDOW_ONLY -- the
@@ -31,7 +32,7 @@ from tests.util import same_window
 pytestmark = pytest.mark.gpu
 
 # groups whose reference is a numpy model, the same in both flavours: computed once from 2^19 rows on, where it takes seconds
-MODELLED = ("field_conversions", "chroma_key", "matte", "transform", "lut3d")
+MODELLED = ("field_conversions", "chroma_key", "matte", "transform", "lut3d", "deinterlace_adaptive", "temporal", "perspective", "ycc422", "ycc420")
 _kept = {}              # case name -> its reference, from the first flavour that asks until the other one has; emptied with the module
 
 
