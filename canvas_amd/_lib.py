@@ -24,6 +24,7 @@ LUT_NONE, LUT_REC709_TO_LINEAR_SCENE, LUT_REC709_TO_LINEAR_DISPLAY, LUT_LINEAR_T
 KEY_SHOW_MATTE = 1                                  # cvs_chroma_key.flags
 MATTE_SHOW, MATTE_MAX_CHOKE, MATTE_MAX_TAPS = 1, 16, 25    # cvs_matte.flags and its limits
 TRANSFORM_NEAREST, TRANSFORM_BILINEAR, TRANSFORM_MAX_COORD = 0, 1, 1 << 23    # cvs_transform.filter and the coordinate limit
+TRANSFORM_CATMULL_ROM = 4                                                   # (the filter's support in samples per axis)
 MAX_COORD, RESAMPLE_MAX_COORD = 1 << 30, 1 << 23        # the coordinate contract of canvas_hip.h: every entry's bound, the resamplers'
 SCOPE_HISTOGRAM, SCOPE_WAVEFORM, SCOPE_PARADE, SCOPE_VECTORSCOPE = range(4)      # cvs_scope.kind
 SCOPE_SKIP_TRANSPARENT, SCOPE_MAX_COLUMNS = 1, 4096                             # cvs_scope.flags and the limit of its columns

@@ -116,6 +116,15 @@ static inline bool cvs_coords_refused(const char *what, const char *operand, con
     }
     return false;
 }
+/* The filters of the two warps (host/transform.c, host/perspective.c), said once so that their windows cannot drift apart: which
+ * values of `filter` there are; how far from a source coordinate a filter's taps reach (nearest: half a pixel; bilinear: i .. i + 1;
+ * Catmull-Rom: i - 1 .. i + 2), which S is grown by for the target window; and the pad of the source window around the mapped
+ * corners of a target window. */
+static inline bool cvs_warp_filter_known(int filter) { return filter == CVS_TRANSFORM_NEAREST || filter == CVS_TRANSFORM_BILINEAR || filter == CVS_TRANSFORM_CATMULL_ROM; }
+static inline double cvs_warp_filter_reach(int filter) { return filter == CVS_TRANSFORM_CATMULL_ROM ? 2.0 : (filter == CVS_TRANSFORM_BILINEAR ? 1.0 : 0.5); }
+static inline double cvs_warp_filter_pad(int filter) { return filter == CVS_TRANSFORM_CATMULL_ROM ? 3.0 : 2.0; }
+#define CVS_WARP_FILTER_REFUSAL "%s: filter %d is none of CVS_TRANSFORM_NEAREST, CVS_TRANSFORM_BILINEAR and CVS_TRANSFORM_CATMULL_ROM"
+
 static inline bool cvs_point_refused(const char *what, const char *operand, v2f p, int lim) {
     if (p.x >= -(float)lim && p.x <= (float)lim && p.y >= -(float)lim && p.y <= (float)lim) return false;
     cvs_set_error("%s: %s: point (%g, %g) lies beyond +-%d", what, operand, p.x, p.y, lim);

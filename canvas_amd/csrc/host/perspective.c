@@ -1,9 +1,9 @@
 /*
  * perspective.c -- cvs_perspective_f32_dev / _f16_dev: the corner pin, a projective warp with the transform's alpha-weighted
- * bilinear filter, and the host arithmetic that goes with it (the nine coefficients from a quad; the target and source windows).
+ * bilinear or Catmull-Rom filter, and the host arithmetic that goes with it (the nine coefficients from a quad; the target and source windows).
  *
  * No reference code.  The contract is DESIGN.md "Corner pin" and the comment of include/canvas_perspective.h; refusals, the
- * windows and the origins stay here, pixels go to kernels/perspective_ops.hip.  All host arithmetic is in double, every
+ * windows and the origins stay here, pixels go to kernels/perspective_ops.hip (Catmull-Rom: kernels/warp_cubic_ops.hip).  All host arithmetic is in double, every
  * operation rounded on its own (this file is compiled with -ffp-contract=off), written in the order DESIGN.md gives so that the
  * numpy model of the tests (tests/perspective_model.py) repeats it exactly.
  */
@@ -12,12 +12,12 @@
 
 #define WINDOW_LIMIT 1073741824.0                       /* 2^30: what a window bound or an origin is clamped to before it becomes an int */
 
-static bool filter_known(int filter) { return filter == CVS_TRANSFORM_NEAREST || filter == CVS_TRANSFORM_BILINEAR; }
+/* (which filters there are, their reach and the source window's pad: internal.h, shared by the two warps) */
 
 /* h widened, with its adjugate over its determinant (the SOURCE -> TARGET map); false with the error set where the contract refuses */
 typedef struct { double h[9], det, f[9]; } projective;
 static bool projective_from(const cvs_perspective *p, projective *a, const char *what) {
-    if (!filter_known(p->filter)) { cvs_set_error("%s: filter %d is neither CVS_TRANSFORM_NEAREST nor CVS_TRANSFORM_BILINEAR", what, p->filter); return false; }
+    if (!cvs_warp_filter_known(p->filter)) { cvs_set_error(CVS_WARP_FILTER_REFUSAL, what, p->filter); return false; }
     if (p->flags != 0) { cvs_set_error("%s: unknown flags 0x%x", what, (unsigned)p->flags); return false; }
     for (int k = 0; k < 9; k++) {
         if (!isfinite(p->h[k])) { cvs_set_error("%s: coefficient h[%d] is not finite", what, k); return false; }
@@ -60,7 +60,7 @@ static void bounds(const double v[4], double pad, int origin, int *lo, int *hi) 
 }
 
 static void target_window(const cvs_perspective *p, const projective *a, const box2i *scur, const box2i *tfull, box2i *win) {
-    const double g = p->filter == CVS_TRANSFORM_BILINEAR ? 1.0 : 0.5;
+    const double g = cvs_warp_filter_reach(p->filter);
     const double x0 = (double)((long long)scur->min.x - p->source_origin[0]) - g, x1 = (double)((long long)scur->max.x - p->source_origin[0]) + g;
     const double y0 = (double)((long long)scur->min.y - p->source_origin[1]) - g, y1 = (double)((long long)scur->max.y - p->source_origin[1]) + g;
     const double sx[4] = { x0, x1, x0, x1 }, sy[4] = { y0, y0, y1, y1 };
@@ -114,8 +114,8 @@ CVS_EXPORT int cvs_perspective_source_window(const cvs_perspective *p, const box
         need->max.x = need->max.y = (int)WINDOW_LIMIT;
         return 0;
     }
-    bounds(u, 2.0, p->source_origin[0], &need->min.x, &need->max.x);
-    bounds(v, 2.0, p->source_origin[1], &need->min.y, &need->max.y);
+    bounds(u, cvs_warp_filter_pad(p->filter), p->source_origin[0], &need->min.x, &need->max.x);
+    bounds(v, cvs_warp_filter_pad(p->filter), p->source_origin[1], &need->min.y, &need->max.y);
     return 0;
 }
 
@@ -130,7 +130,7 @@ CVS_EXPORT int cvs_perspective_from_quad(const double source_rect[4], const doub
         cvs_set_error("cvs_perspective_from_quad: the rectangle (%g, %g)-(%g, %g) is not ascending", source_rect[0], source_rect[1], source_rect[2], source_rect[3]);
         return -1;
     }
-    if (!filter_known(filter)) { cvs_set_error("cvs_perspective_from_quad: filter %d is neither CVS_TRANSFORM_NEAREST nor CVS_TRANSFORM_BILINEAR", filter); return -1; }
+    if (!cvs_warp_filter_known(filter)) { cvs_set_error(CVS_WARP_FILTER_REFUSAL, "cvs_perspective_from_quad", filter); return -1; }
 
     const double tox = clamp_limit(floor(((quad[0][0] + quad[1][0]) + (quad[2][0] + quad[3][0])) / 4.0));
     const double toy = clamp_limit(floor(((quad[0][1] + quad[1][1]) + (quad[2][1] + quad[3][1])) / 4.0));
@@ -234,7 +234,7 @@ static int perspective(void *tdata, const box2i *tfull, box2i *tcur, const void 
     pp.sdx = (long long)p->source_origin[0] - sfull->min.x; pp.sdy = (long long)p->source_origin[1] - sfull->min.y;
     memcpy(pp.h, p->h, sizeof pp.h);
     pp.bilinear = p->filter == CVS_TRANSFORM_BILINEAR;
-    const int rc = cvk_perspective(&pp, half, cvs_pick_stream(stream));
+    const int rc = p->filter == CVS_TRANSFORM_CATMULL_ROM ? cvk_perspective_cubic(&pp, half, cvs_pick_stream(stream)) : cvk_perspective(&pp, half, cvs_pick_stream(stream));
     if (rc != 0) { cvs_set_error("%s: %s", what, hipGetErrorString((hipError_t)rc)); return -1; }
     *tcur = win;
     return 0;

@@ -1,9 +1,9 @@
 /*
- * transform.c -- cvs_transform_f32_dev / _f16_dev: an affine warp with an alpha-weighted bilinear filter, and the host arithmetic
+ * transform.c -- cvs_transform_f32_dev / _f16_dev: an affine warp with an alpha-weighted bilinear or Catmull-Rom filter, and the host arithmetic
  * that goes with it (the coefficients from anchor, scale, rotation and position; the target and source windows).
  *
  * No reference code.  The contract is DESIGN.md "Affine transform" and the comment of include/canvas_hip.h; refusals, the windows
- * and the tile plan stay here, pixels go to kernels/transform_ops.hip.  All window arithmetic is in double, every operation
+ * and the tile plan stay here, pixels go to kernels/transform_ops.hip (Catmull-Rom: kernels/warp_cubic_ops.hip).  All window arithmetic is in double, every operation
  * rounded on its own (this file is compiled with -ffp-contract=off), written in the order DESIGN.md gives so that the numpy model
  * of the tests (tests/transform_model.py) repeats it exactly.
  */
@@ -29,12 +29,12 @@ static void tile_plan(cvk_transform_params *tp) {
 #endif
 }
 
-static bool filter_known(int filter) { return filter == CVS_TRANSFORM_NEAREST || filter == CVS_TRANSFORM_BILINEAR; }
+/* (which filters there are, their reach and the source window's pad: internal.h, shared by the two warps) */
 
 /* m widened, its determinant and the forward (source -> target) map F; false with the error set where the contract refuses */
 typedef struct { double m[6], det, f00, f01, f02, f10, f11, f12; } affine;
 static bool affine_from(const cvs_transform *t, affine *a, const char *what) {
-    if (!filter_known(t->filter)) { cvs_set_error("%s: filter %d is neither CVS_TRANSFORM_NEAREST nor CVS_TRANSFORM_BILINEAR", what, t->filter); return false; }
+    if (!cvs_warp_filter_known(t->filter)) { cvs_set_error(CVS_WARP_FILTER_REFUSAL, what, t->filter); return false; }
     if (t->flags != 0) { cvs_set_error("%s: unknown flags 0x%x", what, (unsigned)t->flags); return false; }
     for (int k = 0; k < 6; k++) {
         if (!isfinite(t->m[k])) { cvs_set_error("%s: coefficient m[%d] is not finite", what, k); return false; }
@@ -72,7 +72,7 @@ static void bounds(const double v[4], double pad, int *lo, int *hi) {
 }
 
 static void target_window(const affine *a, int filter, const box2i *scur, const box2i *tfull, box2i *win) {
-    const double g = filter == CVS_TRANSFORM_BILINEAR ? 1.0 : 0.5;
+    const double g = cvs_warp_filter_reach(filter);
     const double sx[4] = { scur->min.x - g, scur->max.x + g, scur->min.x - g, scur->max.x + g };
     const double sy[4] = { scur->min.y - g, scur->min.y - g, scur->max.y + g, scur->max.y + g };
     double tx[4], ty[4];
@@ -110,8 +110,8 @@ CVS_EXPORT int cvs_transform_source_window(const cvs_transform *t, const box2i *
         u[k] = a.m[0] * tx[k] + a.m[1] * ty[k] + a.m[2];
         v[k] = a.m[3] * tx[k] + a.m[4] * ty[k] + a.m[5];
     }
-    bounds(u, 2.0, &need->min.x, &need->max.x);
-    bounds(v, 2.0, &need->min.y, &need->max.y);
+    bounds(u, cvs_warp_filter_pad(t->filter), &need->min.x, &need->max.x);
+    bounds(v, cvs_warp_filter_pad(t->filter), &need->min.y, &need->max.y);
     return 0;
 }
 
@@ -183,7 +183,7 @@ static int transform(void *tdata, const box2i *tfull, box2i *tcur, const void *s
     memcpy(tp.m, t->m, sizeof tp.m);
     tp.bilinear = t->filter == CVS_TRANSFORM_BILINEAR;
     tile_plan(&tp);
-    const int rc = cvk_transform(&tp, half, cvs_pick_stream(stream));
+    const int rc = t->filter == CVS_TRANSFORM_CATMULL_ROM ? cvk_transform_cubic(&tp, half, cvs_pick_stream(stream)) : cvk_transform(&tp, half, cvs_pick_stream(stream));
     if (rc != 0) { cvs_set_error("%s: %s", what, hipGetErrorString((hipError_t)rc)); return -1; }
     *tcur = win;
     return 0;

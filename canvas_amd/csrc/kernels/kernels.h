@@ -447,6 +447,11 @@ typedef struct {
 } cvk_perspective_params;
 int cvk_perspective(const cvk_perspective_params *pp, int half, void *stream);
 
+/* The Catmull-Rom filter of both warps (warp_cubic_ops.hip, DESIGN.md "Catmull-Rom warps"): the same parameters under the same
+ * conditions; `bilinear` is not read.  The hosts pick the launcher by the filter. */
+int cvk_transform_cubic(const cvk_transform_params *tp, int half, void *stream);
+int cvk_perspective_cubic(const cvk_perspective_params *pp, int half, void *stream);
+
 /* Motion-adaptive deinterlace (deinterlace_ops.hip, DESIGN.md "Adaptive deinterlace"), f16 frames.  `w` (the window written)
  * inside `out` and inside `cw`, cur's current window, itself inside `cur`.  n[j], j < neighbours (1 or 2): the neighbour frames
  * that are present, in either order; v[j] = cw ∩ the neighbour's current window (not empty, inside n[j]): where a sample of

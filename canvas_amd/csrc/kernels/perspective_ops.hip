@@ -17,9 +17,11 @@
 // Shape, as the affine kernel measured and kept (DESIGN.md "Affine transform"): a 256-lane workgroup owns a 32 x 8 tile of
 // target pixels, lanes along x first (a wave covers a 32 x 2 patch whose source footprint is compact under any map), one pixel
 // per lane, taps straight from global memory (one 16-byte load per f32 tap, one 8-byte load per half tap), non-temporal stores,
-// bands of kMaxGridY rows of tiles per launch.  Four instances: f32 / f16 x nearest / bilinear.
+// bands of kMaxGridY rows of tiles per launch.  Four instances: f32 / f16 x nearest / bilinear (the Catmull-Rom filter's two are in
+// warp_cubic_ops.hip: this object holds exactly these four).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "warp_coords.hpp"
 #include "warp_sample.hpp"
 
 namespace {
@@ -27,46 +29,28 @@ namespace {
 using namespace warp;
 using rowstream::rect_empty;
 
-constexpr int kTileW = 32, kTileH = 8, kTileShift = 5;
-
-// relative pixel (x, y) of a view whose first pixel is (-dx, -dy)
-template <int HALF>
-__device__ __forceinline__ char *address(const cvk_view &f, long long dx, long long dy, int x, int y) {
-    return static_cast<char *>(f.data) + ((dy + y) * f.pitch + (dx + x)) * (HALF ? 8 : 16);
-}
-
+// (the pixel of a lane, u, v and the w > 0 rule, and the addresses: warp_coords.hpp, shared with the Catmull-Rom kernel of
+// warp_cubic_ops.hip)
 template <int HALF, int BILINEAR>
 __global__ __launch_bounds__(kThreads) void k_perspective(cvk_perspective_params pp) {
-    const int lx = (int)threadIdx.x & (kTileW - 1), ly = (int)threadIdx.x >> kTileShift;
-    const int x = pp.w.x0 + ((int)blockIdx.x << kTileShift) + lx, y = pp.w.y0 + (int)blockIdx.y * kTileH + ly;
-    if (x > pp.w.x1 || y > pp.w.y1) return;
-    const float fx = (float)x, fy = (float)y;
-    const float nu = (pp.h[0] * fx + pp.h[1] * fy) + pp.h[2], nv = (pp.h[3] * fx + pp.h[4] * fy) + pp.h[5];
-    const float w = (pp.h[6] * fx + pp.h[7] * fy) + pp.h[8];
-    const bool front = w > 0.0f;                                 // false for NaN
-    const v4 o = sample<HALF, BILINEAR>(nu / w, nv / w, Window(pp.s), [&](int i, int j) { return address<HALF>(pp.in, pp.sdx, pp.sdy, i, j); });
-    store<HALF>(address<HALF>(pp.out, pp.tdx, pp.tdy, x, y), front ? o : v4{ 0u, 0u, 0u, 0u });
+    int x, y;
+    if (!pinned_pixel(pp, x, y)) return;
+    float u, v;
+    const bool front = pinned_uv(pp.h, x, y, u, v);
+    const v4 o = sample<HALF, BILINEAR>(u, v, Window(pp.s), [&](int i, int j) { return pinned_address<HALF>(pp.in, pp.sdx, pp.sdy, i, j); });
+    store<HALF>(pinned_address<HALF>(pp.out, pp.tdx, pp.tdy, x, y), front ? o : v4{ 0u, 0u, 0u, 0u });
 }
 
 template <int HALF, int BILINEAR>
-int launch(const cvk_perspective_params &pp, hipStream_t st) { return launch_bands(k_perspective<HALF, BILINEAR>, pp, kTileW, kTileH, st); }
-
-// r + (dx, dy), the rectangle counted from the view's first pixel, lies inside the view
-bool inside_view(const cvk_rect &r, long long dx, long long dy, const cvk_view &v) {
-    return r.x0 + dx >= 0 && r.y0 + dy >= 0 && r.x1 + dx < v.pitch && r.y1 + dy <= (long long)v.fy1 - v.fy0;
-}
+int launch(const cvk_perspective_params &pp, hipStream_t st) { return launch_bands(k_perspective<HALF, BILINEAR>, pp, kPinTileW, kPinTileH, st); }
 
 }  // namespace
 
 extern "C" int cvk_perspective(const cvk_perspective_params *in, int half, void *stream) {
     const cvk_perspective_params &pp = *in;
     if (rect_empty(pp.w)) return 0;
-    if (rect_empty(pp.s)) return (int)hipErrorInvalidValue;
-    const int span = 1 << 23;
-    if (pp.w.x0 < -span || pp.w.y0 < -span || pp.w.x1 > span || pp.w.y1 > span || pp.s.x0 < -span || pp.s.y0 < -span || pp.s.x1 > span || pp.s.y1 > span)
-        return (int)hipErrorInvalidValue;
-    // the window written inside the target's buffer, the source window inside the source's: nothing else is ever addressed
-    if (!inside_view(pp.w, pp.tdx, pp.tdy, pp.out) || !inside_view(pp.s, pp.sdx, pp.sdy, pp.in)) return (int)hipErrorInvalidValue;
+    const int refused = perspective_params_refused(pp);
+    if (refused != 0) return refused;
     hipStream_t st = (hipStream_t)stream;
     if (!pp.bilinear) return half ? launch<1, 0>(pp, st) : launch<0, 0>(pp, st);
     return half ? launch<1, 1>(pp, st) : launch<0, 1>(pp, st);

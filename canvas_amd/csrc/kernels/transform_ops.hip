@@ -16,9 +16,11 @@
 // load at 8-byte alignment from the pair's column clamped to S.x0 .. S.x1 - 1, the lane sorting out which half is which (PAIR) --
 // exists in the diagnostic build only: it measured 1.7 to 1.9 times slower when the plan was chosen, and no slower as it is
 // written now (DESIGN.md "Affine transform", Measured, and its note of 2026-10-20); the built plan has not been changed.
-// One pixel per lane, stores non-temporal.  Four instances: f32 / f16 x nearest / bilinear.
+// One pixel per lane, stores non-temporal.  Four instances: f32 / f16 x nearest / bilinear (the Catmull-Rom filter's two are in
+// warp_cubic_ops.hip: this object holds exactly these four).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "warp_coords.hpp"
 #include "warp_sample.hpp"
 
 namespace {
@@ -28,19 +30,16 @@ using rowstream::rect_empty;
 
 typedef v4 v4_align8 __attribute__((aligned(8)));
 
+// (the pixel of a lane, u and v and the addresses: warp_coords.hpp, shared with the Catmull-Rom kernel of warp_cubic_ops.hip)
 template <int HALF>
-__device__ __forceinline__ char *address(const cvk_view &f, int i, int j) {
-    return static_cast<char *>(f.data) + ((long long)(j - f.fy0) * f.pitch + (i - f.fx0)) * (HALF ? 8 : 16);
-}
+__device__ __forceinline__ char *address(const cvk_view &f, int i, int j) { return affine_address<HALF>(f, i, j); }
 
 template <int HALF, int BILINEAR, int PAIR>
 __global__ __launch_bounds__(kThreads) void k_transform(cvk_transform_params tp) {
-    const int shift = __builtin_ctz((unsigned)tp.tw);
-    const int lx = (int)threadIdx.x & (tp.tw - 1), ly = (int)threadIdx.x >> shift;
-    const int x = tp.w.x0 + ((int)blockIdx.x << shift) + lx, y = tp.w.y0 + (int)blockIdx.y * tp.th + ly;
-    if (x > tp.w.x1 || y > tp.w.y1) return;
-    const float fx = (float)x, fy = (float)y;
-    const float u = (tp.m[0] * fx + tp.m[1] * fy) + tp.m[2], v = (tp.m[3] * fx + tp.m[4] * fy) + tp.m[5];
+    int x, y;
+    if (!affine_pixel(tp, x, y)) return;
+    float u, v;
+    affine_uv(tp.m, x, y, u, v);
     const Window s(tp.s);
     v4 o;
     if (HALF && BILINEAR && PAIR) {
@@ -68,10 +67,8 @@ int launch(const cvk_transform_params &tp, hipStream_t st) { return launch_bands
 extern "C" int cvk_transform(const cvk_transform_params *in, int half, void *stream) {
     const cvk_transform_params &tp = *in;
     if (rect_empty(tp.w)) return 0;
-    if (rect_empty(tp.s) || tp.tw < 8 || tp.tw > kThreads || (tp.tw & (tp.tw - 1)) || tp.tw * tp.th != kThreads) return (int)hipErrorInvalidValue;
-    // the window written inside the target's buffer, the source window inside the source's: nothing else is ever addressed
-    if (tp.w.x0 < tp.out.fx0 || tp.w.y0 < tp.out.fy0 || tp.w.x1 > tp.out.fx1 || tp.w.y1 > tp.out.fy1) return (int)hipErrorInvalidValue;
-    if (tp.s.x0 < tp.in.fx0 || tp.s.y0 < tp.in.fy0 || tp.s.x1 > tp.in.fx1 || tp.s.y1 > tp.in.fy1) return (int)hipErrorInvalidValue;
+    const int refused = transform_params_refused(tp, kThreads);
+    if (refused != 0) return refused;
     hipStream_t st = (hipStream_t)stream;
     if (!tp.bilinear) return half ? launch<1, 0, 0>(tp, st) : launch<0, 0, 0>(tp, st);
     if (!half) return launch<0, 1, 0>(tp, st);

@@ -1,5 +1,6 @@
-// warp_sample.hpp -- what the warp kernels (transform_ops.hip, perspective_ops.hip) share from the source coordinates (u, v) on:
-// the nearest and the alpha-weighted bilinear filter of un-premultiplied RGBA, and the launches of a window of any height.
+// warp_sample.hpp -- what the warp kernels (transform_ops.hip, perspective_ops.hip, warp_cubic_ops.hip) share from the source
+// coordinates (u, v) on: the nearest, the alpha-weighted bilinear and the alpha-weighted Catmull-Rom filter of un-premultiplied
+// RGBA, and the launches of a window of any height.
 //
 // The arithmetic contract, stated here once.  S = the source window in the coordinate system of u and v (every bound within
 // +-2^23, which the callers' hosts see to, so the bounds are exact floats).  In f32 (a half widened exactly), every operation
@@ -14,6 +15,32 @@
 // A tap coordinate is turned into an integer only after it has been clamped into S as a float: NaN, +-Inf and values no int
 // holds never reach a conversion, and no address is ever formed outside S, whatever the coefficients hold.  A tap outside S
 // loads the clamped address and a select drops what it would have added, so the four taps do not diverge at the layer's edge.
+//
+//
+// The Catmull-Rom filter (the cubic that interpolates: on a sample it returns the sample), S, in() and the clamp before any
+// conversion as above, in f32, every product and every sum rounded on its own in both flavours:
+//     i = floorf(u), j = floorf(v);  a = u - i;  b = v - j
+//     weights of a fraction t (wx[0..3] from a, wy[0..3] from b), Horner, in this order:
+//         w0 = ((-0.5f*t + 1.0f)*t - 0.5f)*t        w1 = ((1.5f*t - 2.5f)*t)*t + 1.0f
+//         w2 = ((-1.5f*t + 2.0f)*t + 0.5f)*t        w3 = ((0.5f*t - 0.5f)*t)*t
+//     a == 0 and b == 0:  out = in(i, j) ? source(i, j) code for code : 0                        the copy rule, as bilinear
+//     else  A = R = G = B = 0;  lo_c = +inf, hi_c = -inf per colour channel;  lo_a = +inf, hi_a = -inf
+//           for l in 0..3 (rows j-1+l), for k in 0..3 (columns i-1+k), in this order (the coordinates are the floats
+//           i + (float)(k-1), j + (float)(l-1)):
+//               p = source(i-1+k, j-1+l) if in(...);  counts = in(...) and p.a > 0               false for a NaN alpha
+//               if counts:  q = (wx[k]*wy[l]) * p.a;  A += q;  R += q*p.r;  G += q*p.g;  B += q*p.b
+//                           lo_c = fmin(lo_c, p.c);  hi_c = fmax(hi_c, p.c)                      per colour channel
+//               ta = counts ? p.a : 0;  lo_a = fmin(lo_a, ta);  hi_a = fmax(hi_a, ta)            all 16 positions
+//           out = A > 0 ? (clamp(R/A, lo_r, hi_r), clamp(G/A, ..), clamp(B/A, ..), clamp(A, lo_a, hi_a)) : 0
+//           clamp(t, lo, hi) = fmin(fmax(t, lo), hi);  fmin / fmax: a NaN operand loses;  IEEE divides
+// The clamp rule: the result never leaves the range of the 4 x 4 samples it was made from.  Each colour channel stays between the
+// least and the greatest value of that channel among the taps that count; alpha between the least and greatest alpha of the
+// sixteen positions, one outside S or with an alpha not above 0 counting as 0.  A tap that does not count adds nothing to any
+// sum, so A > 0 implies a counting tap and the colour limits are never the initial infinities.  No negative light out of
+// non-negative light, no alpha above the layer's own, no blow-up of the colour where A collapses under mixed-sign weights; the
+// interior of an opaque layer stays exactly opaque and a flat colour exactly flat (the limits coincide).  What a NaN colour
+// under a positive alpha gives is what the arithmetic above gives; NaN payloads are not pinned, nor is the sign of a zero that
+// a minimum or maximum returns.
 //
 // A kernel computes u and v its own way and says where source(i, j) and the target pixel lie (`at`: (i, j) inside S -> address).
 #pragma once
@@ -113,6 +140,99 @@ __device__ __forceinline__ v4 bilinear(float u, float v, const Window &s, At at)
     const Px p01 = load<HALF>(at(i0, j1));
     const Px p11 = load<HALF>(at(i1, j1));
     return blend<HALF>(t, p00, p10, p01, p11);
+}
+
+// ---------------------------------------------------------------- Catmull-Rom (the contract: the head of this file)
+
+// the four weights of a fraction t, Horner, every product and sum rounded on its own
+__device__ __forceinline__ void cubic_weights(float t, float (&w)[4]) {
+    w[0] = ((-0.5f * t + 1.0f) * t - 0.5f) * t;
+    w[1] = ((1.5f * t - 2.5f) * t) * t + 1.0f;
+    w[2] = ((-1.5f * t + 2.0f) * t + 0.5f) * t;
+    w[3] = ((0.5f * t - 0.5f) * t) * t;
+}
+
+// lo and hi widened by the four values of a tap row; a NaN among them loses, which is how a tap that does not count stays out.
+// (Minima and maxima in any grouping: the same value, the sign of a zero apart.  Written so that each folds into two three-operand
+// instructions.)
+struct Range { float lo, hi; };
+__device__ __forceinline__ void widen_range(Range &r, const float (&t)[4]) {
+    r.lo = fminf(fminf(fminf(t[0], t[1]), t[2]), fminf(fminf(t[3], r.lo), r.lo));
+    r.hi = fmaxf(fmaxf(fmaxf(t[0], t[1]), t[2]), fmaxf(fmaxf(t[3], r.hi), r.hi));
+}
+
+// The source reads the sixteen taps row by row; taps(col, j, p): the four pixels of row j at the columns col[0..3], every one of
+// them inside S, however it loads them.  (hipcc hoists all sixteen loads above the arithmetic all the same: DESIGN.md
+// "Catmull-Rom warps" has the registers.)
+// A tap that does not count is kept out by selects on what goes IN, not on the sums and limits that come out: its alpha becomes 0
+// and its colour 0 for the sums -- q is then +-0 and so is every product (the weights of a finite fraction are finite), and a sum
+// that began at +0 is never -0, so adding +-0 leaves its bits -- and its colour becomes NaN for the limits, where a NaN loses.
+// With u or v not finite the weights are NaN, every tap is outside S, A becomes NaN and A > 0 is false: 0, as the contract says.
+template <int HALF, class Row>
+__device__ __forceinline__ v4 cubic_rows(float u, float v, const Window &s, Row taps) {
+    const float fi = floorf(u), fj = floorf(v), a = u - fi, b = v - fj;
+    float wx[4], wy[4];
+    cubic_weights(a, wx);
+    cubic_weights(b, wy);
+    bool xin[4];
+    int col[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float fk = fi + (float)(k - 1);
+        xin[k] = s.xin(fk);
+        col[k] = s.col(fk);
+    }
+    const float inf = __builtin_inff(), nan = __builtin_nanf("");
+    const v4 zero = { 0u, 0u, 0u, 0u };
+    Sum sum = { 0.0f, 0.0f, 0.0f, 0.0f };
+    Range rr = { inf, -inf }, rg = { inf, -inf }, rb = { inf, -inf }, ra = { inf, -inf };
+    v4 centre = zero;                                           // source(i, j), for the copy rule
+#pragma unroll
+    for (int l = 0; l < 4; l++) {
+        const float fl = fj + (float)(l - 1);
+        const bool yin = s.yin(fl);
+        const int row = s.row(fl);
+        Px p[4];
+        taps(col, row, p);
+        if (l == 1) centre = p[1].raw;
+        float ta[4], tr[4], tg[4], tb[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const cvs::px32 &f = p[k].f;
+            const bool counts = xin[k] && yin && f.a > 0.0f;    // false for a NaN alpha
+            ta[k] = counts ? f.a : 0.0f;
+            const float q = (wx[k] * wy[l]) * ta[k];
+            sum.a = sum.a + q;
+            sum.r = sum.r + q * (counts ? f.r : 0.0f);
+            sum.g = sum.g + q * (counts ? f.g : 0.0f);
+            sum.b = sum.b + q * (counts ? f.b : 0.0f);
+            tr[k] = counts ? f.r : nan;
+            tg[k] = counts ? f.g : nan;
+            tb[k] = counts ? f.b : nan;
+        }
+        widen_range(rr, tr);
+        widen_range(rg, tg);
+        widen_range(rb, tb);
+        widen_range(ra, ta);
+    }
+    v4 o = zero;
+    if (sum.a > 0.0f) {
+        const cvs::px32 c = { clampf(sum.r / sum.a, rr.lo, rr.hi), clampf(sum.g / sum.a, rg.lo, rg.hi), clampf(sum.b / sum.a, rb.lo, rb.hi),
+                              clampf(sum.a, ra.lo, ra.hi) };
+        if (HALF) { const uint2 n = cvs::narrow(c); o = v4{ n.x, n.y, 0u, 0u }; }
+        else o = v4{ __float_as_uint(c.r), __float_as_uint(c.g), __float_as_uint(c.b), __float_as_uint(c.a) };
+    }
+    if (a == 0.0f && b == 0.0f) o = (xin[1] && s.yin(fj)) ? centre : zero;    // on a sample: a copy
+    return o;
+}
+
+// one load per tap: 8 bytes of a half pixel, 16 of an f32 one
+template <int HALF, class At>
+__device__ __forceinline__ v4 cubic(float u, float v, const Window &s, At at) {
+    return cubic_rows<HALF>(u, v, s, [&](const int (&col)[4], int j, Px (&p)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = load<HALF>(at(col[k], j));
+    });
 }
 
 template <int HALF, int BILINEAR, class At>

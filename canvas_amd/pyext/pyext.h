@@ -111,7 +111,7 @@ PyObject *warp_get_part(warp_node *self, void *index);              /* getter an
 int warp_set_part(warp_node *self, PyObject *value, void *index);
 PyObject *warp_get_filter(warp_node *self, void *closure);
 int warp_set_filter(warp_node *self, PyObject *value, void *closure);
-int warp_filter_from(PyObject *v);                                  /* "nearest" / "bilinear" -> CVS_TRANSFORM_*, or -1 with a Python error set */
+int warp_filter_from(PyObject *v);                                  /* "nearest" / "bilinear" / "catmull-rom" -> CVS_TRANSFORM_*, or -1 with a Python error set */
 void warp_render(warp_node *self, int frame_index, rgba_frame_dev *f, const warp_ops *ops);
 /* transparent black over `all` minus `win` (win inside all, or empty) in at most four strips, windows left alone: 0, or -1 */
 int warp_clear_around(rgba_frame_dev *f, const box2i *all, const box2i *win);

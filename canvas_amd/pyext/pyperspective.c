@@ -134,7 +134,7 @@ static PyGetSetDef pin_getset[] = {
     { "source_rect", (getter)warp_get_part, (setter)warp_set_part, "The part of the source that is pinned (box2i or frame function)." },
     { "corners", (getter)pin_get_corners, (setter)pin_set_corners,
       "Where source_rect's top-left, top-right, bottom-right and bottom-left corners land (four pairs or frame functions)." },
-    { "filter", (getter)warp_get_filter, (setter)warp_set_filter, "\"nearest\" or \"bilinear\" (alpha-weighted)." },
+    { "filter", (getter)warp_get_filter, (setter)warp_set_filter, "\"nearest\", \"bilinear\" or \"catmull-rom\" (both alpha-weighted; the cubic never leaves the range of its 4 x 4 samples)." },
     { NULL }
 };
 static PyTypeObject py_type_CornerPin = {

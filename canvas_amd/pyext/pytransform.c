@@ -115,7 +115,7 @@ static PyGetSetDef transform_getset[] = {
     { "scale", (getter)warp_get_part, (setter)warp_set_part, "Scale factors along x and y, negative to mirror (pair or frame function).", PART(PART_SCALE) },
     { "rotation", (getter)warp_get_part, (setter)warp_set_part, "Degrees, clockwise on screen (number or frame function).", PART(PART_ROTATION) },
     { "position", (getter)warp_get_part, (setter)warp_set_part, "Where the anchor lands in the target (pair or frame function).", PART(PART_POSITION) },
-    { "filter", (getter)warp_get_filter, (setter)warp_set_filter, "\"nearest\" or \"bilinear\" (alpha-weighted)." },
+    { "filter", (getter)warp_get_filter, (setter)warp_set_filter, "\"nearest\", \"bilinear\" or \"catmull-rom\" (both alpha-weighted; the cubic never leaves the range of its 4 x 4 samples)." },
     { NULL }
 };
 static PyTypeObject py_type_Transform = {

@@ -87,14 +87,15 @@ int warp_filter_from(PyObject *v) {
     if (v && PyUnicode_Check(v)) {
         if (PyUnicode_CompareWithASCIIString(v, "nearest") == 0) return CVS_TRANSFORM_NEAREST;
         if (PyUnicode_CompareWithASCIIString(v, "bilinear") == 0) return CVS_TRANSFORM_BILINEAR;
-        PyErr_SetString(PyExc_ValueError, "filter is \"nearest\" or \"bilinear\"");
+        if (PyUnicode_CompareWithASCIIString(v, "catmull-rom") == 0) return CVS_TRANSFORM_CATMULL_ROM;
+        PyErr_SetString(PyExc_ValueError, "filter is \"nearest\", \"bilinear\" or \"catmull-rom\"");
         return -1;
     }
-    PyErr_SetString(PyExc_TypeError, "filter is the string \"nearest\" or \"bilinear\"");
+    PyErr_SetString(PyExc_TypeError, "filter is the string \"nearest\", \"bilinear\" or \"catmull-rom\"");
     return -1;
 }
 PyObject *warp_get_filter(warp_node *self, void *closure) {
-    return PyUnicode_FromString(self->filter == CVS_TRANSFORM_NEAREST ? "nearest" : "bilinear");
+    return PyUnicode_FromString(self->filter == CVS_TRANSFORM_NEAREST ? "nearest" : (self->filter == CVS_TRANSFORM_CATMULL_ROM ? "catmull-rom" : "bilinear"));
 }
 int warp_set_filter(warp_node *self, PyObject *v, void *closure) {
     const int filter = warp_filter_from(v);

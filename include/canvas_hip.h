@@ -641,13 +641,13 @@ typedef struct cvs_matte {
 CVS_EXPORT int cvs_matte_refine_f32_dev(rgba_frame_f32 *target, const rgba_frame_f32 *source, const cvs_matte *m, cvs_stream_t s);
 CVS_EXPORT int cvs_matte_refine_f16_dev(rgba_frame_f16 *target, const rgba_frame_f16 *source, const cvs_matte *m, cvs_stream_t s);
 /* Affine transform (DESIGN.md "Affine transform"): rotate, scale, mirror and move a layer of un-premultiplied pixels, the
- * bilinear filter weighted by alpha so that a layer's edge keeps its colour and only its alpha falls off.  Integer coordinates
+ * bilinear and the Catmull-Rom filter weighted by alpha so that a layer's edge keeps its colour and only its alpha falls off.  Integer coordinates
  * are sample positions.  `m` maps TARGET coordinates to SOURCE coordinates.  S = source.current_window; the entry writes
  * win = cvs_transform_target_window(t, S, target.full_window) and sets target.current_window = win (0 is returned for an empty
  * one too, and nothing is launched); pixels of `target` outside win keep what they held.  The output is the crop of the
  * infinite-plane result to win.
  * -1 with a message and an empty target window, before the device is touched, for: a NULL frame or a NULL `t`; a source window
- * outside its full window; a filter other than the two; flags != 0; a non-finite m[k]; m0*m4 - m1*m3 (in double) zero or not
+ * outside its full window; a filter other than the three; flags != 0; a non-finite m[k]; m0*m4 - m1*m3 (in double) zero or not
  * finite; a coordinate of S or of target.full_window beyond +-CVS_TRANSFORM_MAX_COORD (every coordinate is then an exact
  * float); target->data == source->data.
  * Per pixel, in f32 (a half widened exactly), every operation rounded on its own in both arithmetic flavours:
@@ -661,9 +661,28 @@ CVS_EXPORT int cvs_matte_refine_f16_dev(rgba_frame_f16 *target, const rgba_frame
  *                         if in(i + di, j + dj):  p = source(i + di, j + dj);  q = w * p.a;  A = A + q;
  *                                                 R = R + q*p.r;  G = G + q*p.g;  B = B + q*p.b
  *                     out = A != 0 ? (R / A, G / A, B / A, A) : (0, 0, 0, 0)
+ *     CATMULL_ROM (DESIGN.md "Catmull-Rom warps"; the cubic that interpolates: on a sample it returns the sample):
+ *                i = floorf(u), j = floorf(v);  a = u - i;  b = v - j
+ *                weights of a fraction t (wx[0..3] from a, wy[0..3] from b), Horner, in this order:
+ *                    w0 = ((-0.5f*t + 1.0f)*t - 0.5f)*t        w1 = ((1.5f*t - 2.5f)*t)*t + 1.0f
+ *                    w2 = ((-1.5f*t + 2.0f)*t + 0.5f)*t        w3 = ((0.5f*t - 0.5f)*t)*t
+ *                a == 0 and b == 0:  out = in(i, j) ? source(i, j) code for code : (0, 0, 0, 0)
+ *                else A = R = G = B = 0;  lo_c = +inf, hi_c = -inf per colour channel;  lo_a = +inf, hi_a = -inf
+ *                     for l in 0..3 (rows j-1+l), for k in 0..3 (columns i-1+k), in this order:
+ *                         p = source(i-1+k, j-1+l) if in(...);  counts = in(...) and p.a > 0       (false for a NaN alpha)
+ *                         if counts:  q = (wx[k]*wy[l]) * p.a;  A = A + q;  R = R + q*p.r;  G = G + q*p.g;  B = B + q*p.b
+ *                                     lo_c = fmin(lo_c, p.c);  hi_c = fmax(hi_c, p.c)               per colour channel
+ *                         ta = counts ? p.a : 0;  lo_a = fmin(lo_a, ta);  hi_a = fmax(hi_a, ta)      all 16 positions
+ *                     out = A > 0 ? (clamp(R/A, lo_r, hi_r), clamp(G/A, ..), clamp(B/A, ..), clamp(A, lo_a, hi_a)) : (0, 0, 0, 0)
+ *                     clamp(t, lo, hi) = fmin(fmax(t, lo), hi);  fmin / fmax: a NaN operand loses
+ *                The clamp rule: the result never leaves the range of the 4 x 4 samples it was made from -- no negative light out
+ *                of non-negative light, no alpha above the layer's own, an opaque interior stays opaque, a flat colour flat.
  * Taps outside S are skipped and never read.  f16 targets are truncated once, at the store (the copy paths move the code).  The
- * payload of a NaN is not pinned. */
+ * payload of a NaN is not pinned, nor the sign of a zero that a minimum or maximum of the clamp rule returns.  The value of
+ * CVS_TRANSFORM_CATMULL_ROM is the filter's support in samples per axis (6 is left
+ * for a Lanczos-3 filter); 2, 3 and every other value are refused. */
 enum { CVS_TRANSFORM_NEAREST = 0, CVS_TRANSFORM_BILINEAR = 1 };
+enum { CVS_TRANSFORM_CATMULL_ROM = 4 };
 enum { CVS_TRANSFORM_MAX_COORD = 1 << 23 };
 typedef struct cvs_transform {
     float m[6];     /* TARGET -> SOURCE:  u = (m[0]*x + m[1]*y) + m[2];   v = (m[3]*x + m[4]*y) + m[5] */
@@ -679,7 +698,7 @@ CVS_EXPORT int cvs_transform_f16_dev(rgba_frame_f16 *target, const rgba_frame_f1
  * result.
  * _target_window: the target pixels that can have a tap inside `source_current`, clipped to `target_full` (DESIGN.md has the
  * formula).  _source_window: the source pixels the taps of `target_window` can touch.  Both return 0, or -1 with a message and
- * an empty box for a NULL argument, a filter other than the two, a non-finite coefficient or a determinant that is zero or not
+ * an empty box for a NULL argument, a filter other than the three, a non-finite coefficient or a determinant that is zero or not
  * finite. */
 CVS_EXPORT int cvs_transform_from_parts(const double anchor[2], const double scale[2], double rotation_degrees, const double position[2], float m[6]);
 CVS_EXPORT int cvs_transform_target_window(const cvs_transform *t, const box2i *source_current, const box2i *target_full, box2i *win);

@@ -24,12 +24,12 @@ extern "C" {
  *     then NEAREST / BILINEAR exactly as cvs_transform (canvas_hip.h) with in() tested against S' and source(i, j) the pixel
  *     at (source_origin.x + i, source_origin.y + j): the copy rule on a sample (a == 0 and b == 0), alpha-weighted taps in
  *     the order (0,0), (1,0), (0,1), (1,1), A != 0 ? (R/A, G/A, B/A, A) : 0, one truncation at an f16 store, and a tap outside
- *     S' is never read.
+ *     S' is never read.  CATMULL_ROM likewise: the sixteen taps, the copy rule and the clamp rule of cvs_transform.
  * With h6 = h7 = 0 and h8 = 1, w is exactly 1 and u = nu; with both origins (0, 0) as well the entries give cvs_transform's bytes.
  * The entry writes win = cvs_perspective_target_window(p, S, target.full_window) and sets target.current_window = win; pixels
  * outside win keep what they held.  An empty S or win: 0, an empty window, nothing launched.
  * Refused with -1 and a message, before the device is touched, the target's window set empty: a NULL argument; a source window
- * outside its buffer; a filter other than the two; flags != 0; an h[k] that is not finite; a determinant of h (in double) that is
+ * outside its buffer; a filter other than the three; flags != 0; an h[k] that is not finite; a determinant of h (in double) that is
  * zero or not finite; a coordinate beyond +-CVS_MAX_COORD; any coordinate of target.full_window - target_origin or of
  * S - source_origin (formed in 64 bit) beyond +-CVS_PERSPECTIVE_MAX_SPAN; target->data == source->data. */
 enum { CVS_PERSPECTIVE_MAX_SPAN = 1 << 23 };
@@ -37,7 +37,7 @@ typedef struct cvs_perspective {
     float h[9];              /* TARGET -> SOURCE, both relative to the origins below */
     int   target_origin[2];  /* x, y */
     int   source_origin[2];
-    int   filter;            /* CVS_TRANSFORM_NEAREST / CVS_TRANSFORM_BILINEAR */
+    int   filter;            /* CVS_TRANSFORM_NEAREST / CVS_TRANSFORM_BILINEAR / CVS_TRANSFORM_CATMULL_ROM */
     int   flags;             /* none defined: 0 */
 } cvs_perspective;
 /* a target that is the source's buffer is refused: canvas_hip.h "Operands that share a buffer" */

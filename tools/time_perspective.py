@@ -8,7 +8,9 @@ alternating rounds:
     keystone_f16       top edge 0.6 of the bottom, centred: w varies along y
     general_f16        a general convex quad inside the frame
     identity_f32 / keystone_f32 / general_f32                          the same on f32 frames (16 B + 16 B per pixel)
-All pins bilinear.  One JSON line per (op, size): microseconds per call (median round, min, max, and every round), the bytes of
+    keystone_cubic_f16 / general_cubic_f16                             the two quads under the Catmull-Rom filter (sixteen taps where
+                       bilinear has four), each beside its bilinear row in the same rounds; `vs_bilinear` is the ratio of the medians
+All other pins bilinear.  One JSON line per (op, size): microseconds per call (median round, min, max, and every round), the bytes of
 the window written (read once, written once) over the median as a fraction of 8 TB/s, the window's share of the frame, the ratios
 to gain_offset and to rot30_f16 of the same run, and gain_offset's own min-max spread relative to its median: the margin within
 which "costs the same" is meant.
@@ -28,6 +30,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canvas_amd import _lib  # noqa: E402
+from tests import cubic_model as cm  # noqa: E402
 from tests import key_model as km  # noqa: E402
 from tests import perspective_model as pm  # noqa: E402
 from tests import transform_model as tm  # noqa: E402
@@ -74,10 +77,10 @@ def main():
         def share_of(win):
             return (win[2] - win[0] + 1) * (win[3] - win[1] + 1) / float(w * h)
 
-        def pin(quad, half=True):
+        def pin(quad, half=True, filt=pm.BILINEAR):
             triple = pm.from_quad(pm.outer(full), quad)
-            p = _lib.perspective(*triple, filter=pm.BILINEAR)
-            share = share_of(pm.target_window(triple, pm.BILINEAR, full, full))
+            p = _lib.perspective(*triple, filter=filt)
+            share = share_of(cm.perspective_target_window(triple, full, full) if filt == _lib.TRANSFORM_CATMULL_ROM else pm.target_window(triple, filt, full, full))
             if half:
                 return (lambda i: lib.cvs_perspective_f16_dev(t16[i % n16].ref(), s16[i % n16].ref(), C.byref(p), stream)), 16, share
             return (lambda i: lib.cvs_perspective_f32_dev(t32[i % n32].ref(), s32[i % n32].ref(), C.byref(p), stream)), 32, share
@@ -91,6 +94,7 @@ def main():
         ops = [("gain_offset", (lambda i: lib.cvs_gain_offset_f16_dev(t16[i % n16].ref(), s16[i % n16].ref(), 1.25, 0.0625, stream), 16, 1.0)),
                ("rot30_f16", rot30)]
         ops += [(name + "_f16", pin(quad)) for name, quad in quads] + [(name + "_f32", pin(quad, half=False)) for name, quad in quads]
+        ops += [(name + "_cubic_f16", pin(quad, filt=_lib.TRANSFORM_CATMULL_ROM)) for name, quad in quads[1:]]
         times = {name: [] for name, _ in ops}
         for name, (call, _, _) in ops:
             for i in range(args.warmup):
@@ -116,6 +120,8 @@ def main():
                     "vs_rot30_f16": round(statistics.median(ratios), 3), "gain_offset_spread": round(margin, 3), "window_share": round(share, 3),
                     "fraction_of_8TBps_on_%dBpx" % px: round(share * w * h * px / (ms * 1e-3) / PEAK, 3),
                     "frames_f16": n16, "frames_f32": n32, "calls": args.calls}
+            if "_cubic" in name:
+                line["vs_bilinear"] = round(ms / statistics.median(times[name.replace("_cubic", "")]), 3)
             print(json.dumps(line), flush=True)
         for f in s16 + t16 + s32 + t32:
             f.free()

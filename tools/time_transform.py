@@ -9,7 +9,11 @@ alternating rounds:
     rot90_f16          f16 frames, 90 degrees about the centre       the copy path, columns read along rows
     half_f16           f16 frames, scale 0.5 about the centre, bilinear
     rot30_near_f16     f16 frames, 30 degrees, nearest
+    double_f16         f16 frames, scale 2 about the centre, bilinear
     rot30_f32          f32 frames, 30 degrees, bilinear (16 B + 16 B per pixel)
+    shift_cubic_f16, rot30_cubic_f16, half_cubic_f16, double_cubic_f16, rot30_cubic_f32
+                       the same maps under the Catmull-Rom filter (sixteen taps where bilinear has four), each beside its bilinear
+                       row in the same rounds; `vs_bilinear` is the ratio of the two medians
 One JSON line per (op, size): microseconds per call (median round, min, max, and every round), the bytes of the window written
 (read once, written once) over the median as a fraction of 8 TB/s, the window's share of the frame, the ratio to gain_offset
 in the same run, and gain_offset's own min-max spread relative to its median: the margin within which "costs the same" is meant.
@@ -33,6 +37,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canvas_amd import _lib  # noqa: E402
 from canvas_amd.abi import v2f  # noqa: E402
+from tests import cubic_model as cm  # noqa: E402
 from tests import key_model as km  # noqa: E402
 from tests import transform_model as tm  # noqa: E402
 from tests.models import f2h_rz_model  # noqa: E402
@@ -40,6 +45,7 @@ from tests.models import f2h_rz_model  # noqa: E402
 SIZES = [(3840, 2160), (1920, 1080)]
 PEAK = 8.0e12
 ROTATE_BYTES = 288 << 20
+CUBIC = _lib.TRANSFORM_CATMULL_ROM
 SHOT = dict(tolerance=0.08, softness=0.25, spill=0.8, spill_range=0.4)
 
 
@@ -82,7 +88,7 @@ def main():
 
         def warp(parts, filt, half=True):
             t = _lib.transform(tm.from_parts(**parts), filt)
-            win = tm.target_window(tuple(t.m), filt, full, full)
+            win = cm.transform_target_window(tuple(t.m), full, full) if filt == CUBIC else tm.target_window(tuple(t.m), filt, full, full)
             share = (win[2] - win[0] + 1) * (win[3] - win[1] + 1) / float(w * h)
             if half:
                 return (lambda i: lib.cvs_transform_f16_dev(t16[i % n16].ref(), s16[i % n16].ref(), C.byref(t), stream)), 16, share
@@ -95,7 +101,13 @@ def main():
                ("rot90_f16", warp(dict(mid, rotation=90), tm.BILINEAR)),
                ("half_f16", warp(dict(mid, scale=(0.5, 0.5)), tm.BILINEAR)),
                ("rot30_near_f16", warp(dict(mid, rotation=30), tm.NEAREST)),
-               ("rot30_f32", warp(dict(mid, rotation=30), tm.BILINEAR, half=False))]
+               ("double_f16", warp(dict(mid, scale=(2, 2)), tm.BILINEAR)),
+               ("rot30_f32", warp(dict(mid, rotation=30), tm.BILINEAR, half=False)),
+               ("shift_cubic_f16", warp(dict(position=(0.5, 0.5)), CUBIC)),
+               ("rot30_cubic_f16", warp(dict(mid, rotation=30), CUBIC)),
+               ("half_cubic_f16", warp(dict(mid, scale=(0.5, 0.5)), CUBIC)),
+               ("double_cubic_f16", warp(dict(mid, scale=(2, 2)), CUBIC)),
+               ("rot30_cubic_f32", warp(dict(mid, rotation=30), CUBIC, half=False))]
         digests = {}
         for plan in plans or [None]:
             if plan:
@@ -125,6 +137,8 @@ def main():
                         "gain_offset_spread": round(margin, 3), "window_share": round(share, 3),
                         "fraction_of_8TBps_on_%dBpx" % px: round(share * w * h * px / (ms * 1e-3) / PEAK, 3),
                         "frames_f16": n16, "frames_f32": n32, "calls": args.calls}
+                if "_cubic" in name:
+                    line["vs_bilinear"] = round(ms / statistics.median(times[name.replace("_cubic", "")]), 3)
                 print(json.dumps(line), flush=True)
         differing = sorted(name for name, seen in digests.items() if len(seen) != 1)
         print(json.dumps({"size": "%dx%d" % (w, h), "plans": plans or ["built-in"], "ops_whose_bytes_differ_between_plans": differing}), flush=True)
